@@ -8,8 +8,14 @@ steps, inputs (weights, game states) resident in HBM when the timed region start
 outputs -- all_memories, alpha_parallel.rs:215-230: relabelled, ordered MemoryFragments -- DELIVERED
 in host memory when it ends (`value_hbm_only`: the same batches with the records left in HBM).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3}] [--games G] [--iterations I]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3}] [--games G] [--iterations I] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what `value` needs and no more: set-up, the primer, W warm-up steps, the K timed steps, the line.  `--full` adds the
+legs that take runs of their own -- the HBM-only repeat (`value_hbm_only`), the batches played side by side (`value_pipelined`) and the
+CPU baseline (`cpu_baseline`); --hbm-only-steps, --pipeline, --no-cpu-baseline and --cpu-games size or drop them there.
+`--dump-outputs DIR` writes the records of the LAST timed step (what the caller of that self_play_parallel call receives) as
+DIR/<name>.npy after the timed region, for comparing two builds output for output (dump_outputs).
 
 `python bench.py --gpus N` typed alone (N > 1, no RANK in the environment) starts its own N ranks -- a child torch.distributed.run on
 127.0.0.1 and a free port, before anything that could touch a GPU is imported -- and passes rank 0's line through (launch_ranks).
@@ -269,6 +275,31 @@ def learn_loop_leg(eng, games, iterations, timeout_s=3000):
         return {"failed": f"no result within {timeout_s} s"}
 
 
+DUMP_BYTES = 48 << 20         # --dump-outputs: what the .npy files may hold together (the limit is 64 MB)
+DUMP_NAMES = ("outcome", "ps", "state", "game")     # a MemoryFragment's fields, one row per fragment (alpha_parallel.rs:215-230)
+
+
+def dump_outputs(dirname, o, seed):
+    """--dump-outputs: the records one self_play_parallel call delivered -> DIR/outcome.npy, ps.npy, state.npy (float32), game.npy and
+    rows.npy (float64).  All rows while they fit DUMP_BYTES; otherwise the SAME rows of every array, drawn without replacement by a
+    generator seeded with --seed and sorted: two builds that deliver the same records write the same files.  rows.npy holds the
+    row numbers written.  Returns what the line says about it."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {k: np.asarray(o[k]) for k in DUMP_NAMES}
+    n = len(arrs["outcome"])
+    kinds = {k: np.float64 if a.dtype.itemsize > 2 and a.dtype.kind in "iu" else np.float32 for k, a in arrs.items()}     # (u32 game ids: exact in float64)
+    row_bytes = 8 + sum(int(np.prod(a.shape[1:])) * np.dtype(kinds[k]).itemsize for k, a in arrs.items())
+    keep = min(n, DUMP_BYTES // row_bytes)
+    rows = np.arange(n) if keep == n else np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+    written = 0
+    for k, a in list(arrs.items()) + [("rows", rows)]:
+        out = np.ascontiguousarray((a if k == "rows" or keep == n else a[rows]).astype(np.float64 if k == "rows" else kinds[k]))
+        np.save(os.path.join(dirname, k + ".npy"), out)
+        written += out.nbytes
+    return {"dir": dirname, "files": [k + ".npy" for k in DUMP_NAMES + ("rows",)], "rows_delivered": n, "rows_written": int(keep), "bytes": written}
+
+
 PRESETS = {   # BASELINE.json configs[] that are self-play runs (configs[0] = tic-tac-toe plumbing, configs[4] = the learn loop: --learn-loop)
     1: dict(games=1024, iterations=100, name="configs[1]: backgammon, num_self_play_batches=1024, iterations=100, 1 GPU (the metric's own configuration)"),
     2: dict(games=1024, iterations=400, name="configs[2]: backgammon, num_self_play_batches=8192 over 8 GPUs = 1024 per GPU, iterations=400"),
@@ -393,21 +424,29 @@ def main(argv=None, engine_factory=None):
     ap.add_argument("--games", type=int, default=None, help="num_self_play_batches per GPU (overrides the preset)")
     ap.add_argument("--iterations", type=int, default=None, help="MCTS iterations (overrides the preset)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0xD1EE0001)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the legs beside the headline figure: the HBM-only repeat (--hbm-only-steps), the batches played "
+                    "side by side (--pipeline) and the CPU baseline (--no-cpu-baseline drops it); a plain run times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the records the last of them delivered as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB: a fixed, seeded sample of the rows when there are more; rank 0's)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-games", type=int, default=16, help="games the CPU baseline also plays through the real self-play loop to a ply cap (measured plies/s; 0 = extrapolation only)")
     ap.add_argument("--plies-per-game", type=float, default=0.0, help=argparse.SUPPRESS)
     ap.add_argument("--max-steps", type=int, default=0, help="profiling aid: stop each batch after this many move-steps (0 = play to completion)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--exp-per-game", type=float, default=0.0, help=argparse.SUPPRESS)
-    ap.add_argument("--pipeline", type=int, default=4, help="also time K batches played side by side through diee_self_play_multi "
+    ap.add_argument("--pipeline", type=int, default=4, help="--full: also time K batches played side by side through diee_self_play_multi "
                     "(self_play_iterations of the learn loop; 0 = skip); reported as value_pipelined, never as value")
-    ap.add_argument("--hbm-only-steps", type=int, default=2, help="also repeat this many of the timed batches (same seeds) with the records left in HBM: "
+    ap.add_argument("--hbm-only-steps", type=int, default=2, help="--full: also repeat this many of the timed batches (same seeds) with the records left in HBM: "
                     "value_hbm_only / output_delivery_ms (0 = skip)")
     ap.add_argument("--learn-loop", action="store_true", help="also run BASELINE configs[4] (learn_iterations=2, self_play_iterations=4, num_epochs=4, "
                     "training_batch_size=256) after the self-play legs and report its wall-clock per phase as `learn_loop` (adds minutes)")
     ap.add_argument("--learn-games", type=int, default=None, help="num_self_play_batches of the --learn-loop run (default: --games)")
     ap.add_argument("--launch-timeout", type=float, default=0.0, help="N > 1 typed alone: stop the ranks this process started after so many seconds (0 = never)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if not args.full:                            # a plain run: the K timed steps and the line, none of the legs beside them
+        args.hbm_only_steps, args.pipeline, args.no_cpu_baseline = 0, 0, True
     preset = PRESETS[args.config]
     custom = args.games is not None or args.iterations is not None
     if args.games is None:
@@ -521,9 +560,10 @@ def main(argv=None, engine_factory=None):
                 import torch
                 torch.cuda.synchronize()
 
-    def run_step(i, fetch=True):
+    def run_step(i, fetch=True, hold=None):
         """one self_play_parallel call as a host binding the C ABI makes it: the call returns with the MemoryFragments in
-        engine-owned host arrays (fetch) -- looked at, handed back -- or with the records left in HBM (the HBM-only leg)"""
+        engine-owned host arrays (fetch) -- looked at, handed back -- or with the records left in HBM (the HBM-only leg).
+        hold (a list, --dump-outputs): the records are handed back later, by hand_back()"""
         t = time.perf_counter()
         with turn:
             o = eng.self_play_parallel(args.games, cfg, 1.25, args.seed + 0x9E37 * i, ref_quirks=True,
@@ -531,8 +571,17 @@ def main(argv=None, engine_factory=None):
         st = o["stats"]
         if fetch:
             assert len(o["outcome"]) == st["fragments"] and o["ps"].shape == (st["fragments"], 1352), "delivered records != counted records"
-            o.get("free", lambda: None)()
+            if hold is not None:
+                hold.append(o)
+            else:
+                o.get("free", lambda: None)()
         return st, time.perf_counter() - t
+
+    def hand_back(o):
+        """the hand-over a held step skipped; returns the seconds it took (they belong to that step)"""
+        t = time.perf_counter()
+        o.get("free", lambda: None)()
+        return time.perf_counter() - t
 
     def add(tot, st):
         for k, v in st.items():
@@ -547,12 +596,21 @@ def main(argv=None, engine_factory=None):
     barrier()
     t0 = time.perf_counter()
     tot, step_s = {}, []
+    held = [] if args.dump_outputs else None        # the last step's records stay with this process until they are written
     for i in range(args.steps):
-        st, ds = run_step(i)                        # the call returns after its last record has landed in host memory
+        st, ds = run_step(i, hold=held if i == args.steps - 1 else None)      # the call returns after its last record has landed in host memory
         step_s.append(ds)
         add(tot, st)
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if held:
+        # outside the timed region: write the records, then hand them back -- the hand-over is part of a step, so its time joins the clock
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, held[0], args.seed)
+        ds = hand_back(held.pop())
+        step_s[-1] += ds
+        dt += ds
 
     # ---- the same batches with the records left in HBM (what earlier rounds timed): what delivery costs ----
     hbm = None
@@ -781,6 +839,9 @@ def main(argv=None, engine_factory=None):
                                            "default copy=True adds one host memcpy of the records (~645 MB per batch) on the consumer's side, outside `value`")
             out["output_delivery"].update(hbm_only_steps=hbm["steps"], same_seed_delta_ms=hbm["same_seed_delta_ms"],
                                           delivered_over_hbm_only=(hbm["seconds"] / hbm["steps"]) / (sum(step_s[:hbm["steps"]]) / hbm["steps"]))
+        out["full"] = args.full                      # False: a plain run, the legs beside `value` (value_hbm_only, value_pipelined, cpu_baseline) were not run
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if affinity is not None:
             out["host_affinity_rank0"] = affinity
         out["scale_note"] = ("N>1 never run on hardware by the build (gpurun boxes have one GPU); ranks are independent workers (no data-path collective): expected weak scaling = N x the 1-GPU value; "

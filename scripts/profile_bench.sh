@@ -1,7 +1,7 @@
 #!/bin/bash
 # Profiles of the default bench command for profiles/ (run on the GPU box from the repo root):
 #   scripts/profile_bench.sh TAG    ->  gpurun_out/TAG_kernel_stats.csv, TAG_line.json, TAG_headline_kernel_stats.csv, TAG_headline_line.json, TAG_pmc_traffic*.json
-# Pass 1: rocprofv3 --kernel-trace --stats of `python3 bench.py --no-cpu-baseline` (whole run: headline batch + pipelined).
+# Pass 1: rocprofv3 --kernel-trace --stats of `python3 bench.py --full --no-cpu-baseline` (whole run: headline batch + pipelined).
 # Pass 2/3: --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel trace only) of the first move-step at 1024 and 32 boards.
 set -u
 TAG=${1:-r02}
@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 W=/tmp/prof_$TAG; rm -rf "$W"; mkdir -p "$W"
-rocprofv3 --kernel-trace --stats -d "$W/full" --output-format csv -- python3 "$ROOT/bench.py" --no-cpu-baseline > "$OUT/${TAG}_line.json" 2> "$OUT/${TAG}_err.log"
+rocprofv3 --kernel-trace --stats -d "$W/full" --output-format csv -- python3 "$ROOT/bench.py" --full --no-cpu-baseline > "$OUT/${TAG}_line.json" 2> "$OUT/${TAG}_err.log"
 cp "$(find "$W/full" -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_kernel_stats.csv"
 # Pass 1b: the timed leg alone (one batch at a time, records delivered; no HBM-only repeat): k_tower16<4,8,3>'s AverageNs here is what roofline.avg_launch_us must agree with
 rocprofv3 --kernel-trace --stats -d "$W/headline" --output-format csv -- python3 "$ROOT/bench.py" --no-cpu-baseline --pipeline 0 --hbm-only-steps 0 > "$OUT/${TAG}_headline_line.json" 2>> "$OUT/${TAG}_err.log"

@@ -156,7 +156,7 @@ def _bench_worker(rank, world, port, q):
     import bench
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--games", "3", "--iterations", "5", "--pipeline", "2",
+        bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--games", "3", "--iterations", "5", "--full", "--pipeline", "2",
                     "--no-cpu-baseline"], engine_factory=_StubEngine)
     q.put((rank, buf.getvalue()))
 
@@ -212,7 +212,7 @@ def _bench_worker8(rank, world, port, q):
     import bench
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "1", "--warmup", "0", "--games", "2", "--iterations", "4", "--pipeline", "2",
+        bench.main(["--gpus", str(world), "--steps", "1", "--warmup", "0", "--games", "2", "--iterations", "4", "--full", "--pipeline", "2",
                     "--hbm-only-steps", "1", "--no-cpu-baseline"], engine_factory=_StubEngine)
     q.put((rank, buf.getvalue()))
 
