@@ -1200,12 +1200,13 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
     const int root_player = st_player(rs);
     // Q14's count of stale INITIAL slots matters to the batch's first slot for iterations before every game of the batch has had a real
     // selection: `fsel` = the latest first selection in the batch as the previous launches left it (a conservative bound: later is safe)
+    // (k_free_first_sel wrote every game's word before round 0: another game's record -- S.sel -- is rewritten by its own workgroup when it leaves
+    // the launch, which may be before this one gets here)
     uint32_t fsel = 0;
-    if (A.q == 0) { if (lane == 0) F.first_sel[slot] = sel == kNone ? kNone : 0u; }
     if (quirks && slot == seg_first) {
         uint32_t m = 0;
         for (uint32_t g = seg_first + (uint32_t)lane; g < seg_end; g += 64) {
-            const uint32_t f = A.q == 0 ? (S.sel[g] == kNone ? kNone : 0u) : F.first_sel[g];
+            const uint32_t f = F.first_sel[g];
             m = f == kNone ? 0x7fffffffu : (f > m ? f : m);
             if (f == kNone) break;
         }
@@ -1390,6 +1391,33 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                 const uint32_t k = hdr_nch(mt);
                 if (k == 0) break;
                 const float sq = sqrtf(nvis);
+                if (k <= 64u && fcn + k <= ln) {
+                    // The usual level -- one child per lane, all of them in LDS --: the same scores, the same fold (the last of the equal maxima
+                    // among the children behind the last NaN, else that NaN), found with one maximum and two ballots instead of two all-reductions
+                    // of (score, index) pairs; the children's headers are read with their statistics, so the chosen child's header and visits
+                    // come from its lane, not from another trip to LDS.  (a wave alone on its SIMD pays every instruction of the chain in full)
+                    const bool valid = (uint32_t)lane < k;
+                    const uint32_t ci = fcn + (valid ? (uint32_t)lane : 0u);
+                    const float vis = lvis[ci], val = lval[ci], pr = lpri[ci];
+                    const uint32_t ch = lhdr[ci];
+                    const float q = vis == 0.0f ? 0.0f : val / vis;
+                    const float t = sq / (vis + 1.0f);
+                    const float u = c * t;
+                    const float w = u * pr;
+                    const float sc_ = q + w;
+                    const unsigned long long nans = __ballot(valid && sc_ != sc_);
+                    const int lastnan = nans ? 63 - __clzll((long long)nans) : -1;
+                    const bool comp = valid && sc_ == sc_ && lane > lastnan;
+                    const float mx = wave_allmax_f32(comp ? sc_ : -INFINITY);
+                    const unsigned long long win = __ballot(comp && sc_ == mx);
+                    const int chosen = win ? 63 - __clzll((long long)win) : lastnan;
+                    node = fcn + (uint32_t)chosen;
+                    ++depth;
+                    if ((uint32_t)lane == depth) mine = node;
+                    mt = (uint32_t)__builtin_amdgcn_readlane((int)ch, chosen); fcn = hdr_fc(mt);
+                    nvis = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, vis), chosen));
+                    continue;
+                }
                 Best b{0.0f, -1};
                 int lastnan = -1;
                 for (uint32_t j = lane; j < k; j += 64) {
@@ -1492,10 +1520,98 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
         uint32_t ncand = 0;
         if (want > 0 && steps_max > 0) {
             const uint32_t nu = used < ln ? used : ln;
-            for (uint32_t i = lane; i < nu; i += 64) { vvis[i] = lvis[i]; vval[i] = lval[i]; }
+            for (uint32_t i0 = 0; i0 < nu; i0 += 256) {             // four rounds of reads in flight before the first write, as in the staging above
+                float a[4], b[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { const uint32_t i = i0 + 64u * u + (uint32_t)lane; a[u] = lvis[i < nu ? i : 0u]; b[u] = lval[i < nu ? i : 0u]; }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { const uint32_t i = i0 + 64u * u + (uint32_t)lane; if (i < nu) { vvis[i] = a[u]; vval[i] = b[u]; } }
+            }
             __syncthreads();
             const uint32_t demanded = dem ? leaf : kNone;
             uint32_t fruitless = 0;
+            const uint32_t h0 = X.hdr(0), k0 = hdr_nch(h0), fc0 = hdr_fc(h0);
+            const bool resident = used <= ln && k0 >= 1u && k0 <= 64u;       // (uniform)
+            // The usual case -- the whole tree is in LDS, the root's children fit one per lane --: the same rule on the same numbers with the
+            // round trips taken out of the chain.  The root level lives in registers (lane j keeps child j, patched on every virtual visit); a
+            // level below reads everything about a child in ONE trip (statistics, header, evaluation), so the chosen child's header and
+            // visits come from the lane that scored it, not from a second trip; the path's statistics stay in the lanes that record it (a
+            // virtual visit is a store, not a read-modify-write); the candidates found sit one per lane.  No loads from the arena in the loop.
+            if (resident) {
+                auto rl_u = [](uint32_t v_, int l_) { return (uint32_t)__builtin_amdgcn_readlane((int)v_, l_); };
+                auto rl_f = [](float v_, int l_) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v_), l_)); };
+                const bool rc = (uint32_t)lane < k0;
+                const uint32_t rci = fc0 + (rc ? (uint32_t)lane : 0u);
+                float r_vis = vvis[0], c_vis = vvis[rci], c_val = vval[rci];
+                const float c_pri = lpri[rci], c_cval = lcval[rci];
+                const uint32_t c_hdr = lhdr[rci], c_crow = lcrow[rci];
+                uint32_t my_cand = kNone;
+                for (uint32_t step = 0; step < steps_max && ncand < want && fruitless < 8; ++step) {
+                    // (one child per lane: the last of the equal maxima = the highest lane that holds the wave's maximum)
+                    auto last_max = [&](bool comp, float sc_, uint32_t k_) {
+                        const float mx = wave_allmax_f32(comp ? sc_ : -INFINITY);
+                        const unsigned long long win = __ballot(comp && sc_ == mx);
+                        return win ? 63 - __clzll((long long)win) : (int)k_ - 1;
+                    };
+                    int j0;
+                    {
+                        const float sq = __builtin_amdgcn_sqrtf(r_vis);
+                        const float q = c_vis == 0.0f ? 0.0f : c_val * __builtin_amdgcn_rcpf(c_vis);
+                        const float sc_ = q + (c * (sq * __builtin_amdgcn_rcpf(c_vis + 1.0f))) * c_pri;
+                        j0 = last_max(rc && sc_ == sc_, sc_, k0);
+                    }
+                    uint32_t node = fc0 + (uint32_t)j0, depth = 1, mine = kNone, mt = h0;
+                    uint32_t hn = rl_u(c_hdr, j0), ncr = rl_u(c_crow, j0);
+                    float pvis = rl_f(c_vis, j0), pval = 0.0f, ncv = rl_f(c_cval, j0), mvis = 0.0f, mval = 0.0f;
+                    for (;;) {
+                        mt = hn;
+                        const uint32_t k = hdr_nch(mt);
+                        if (k == 0) break;
+                        const uint32_t fcn = hdr_fc(mt);
+                        const float sq = __builtin_amdgcn_sqrtf(pvis);
+                        if (k <= 64u) {
+                            const bool valid = (uint32_t)lane < k;
+                            const uint32_t ci = fcn + (valid ? (uint32_t)lane : 0u);
+                            const float vis = vvis[ci], val = vval[ci], pr = lpri[ci], cv = lcval[ci];
+                            const uint32_t h = lhdr[ci], cr = lcrow[ci];
+                            const float q = vis == 0.0f ? 0.0f : val * __builtin_amdgcn_rcpf(vis);
+                            const float sc_ = q + (c * (sq * __builtin_amdgcn_rcpf(vis + 1.0f))) * pr;
+                            const int lw = last_max(valid && sc_ == sc_, sc_, k);
+                            node = fcn + (uint32_t)lw;
+                            hn = rl_u(h, lw); ncr = rl_u(cr, lw); pvis = rl_f(vis, lw); pval = rl_f(val, lw); ncv = rl_f(cv, lw);
+                            ++depth;
+                            if ((uint32_t)lane == depth) { mine = node; mvis = pvis; mval = pval; }
+                            if (depth >= 63) break;
+                            continue;
+                        }
+                        Best b{0.0f, -1};                           // (more than 64 children -- rare --: the general fold, then one more trip for the chosen child)
+                        for (uint32_t j = lane; j < k; j += 64) {
+                            const uint32_t ci = fcn + j;
+                            const float vis = vvis[ci], val = vval[ci];
+                            const float q = vis == 0.0f ? 0.0f : val * __builtin_amdgcn_rcpf(vis);
+                            const float sc_ = q + (c * (sq * __builtin_amdgcn_rcpf(vis + 1.0f))) * lpri[ci];
+                            if (sc_ == sc_ && (b.j < 0 || !(b.s > sc_))) { b.s = sc_; b.j = (int)j; }
+                        }
+                        b = wave_best(b);
+                        node = fcn + (uint32_t)(b.j >= 0 ? b.j : (int)k - 1);
+                        hn = lhdr[node]; ncr = lcrow[node]; pvis = vvis[node]; pval = vval[node]; ncv = lcval[node];
+                        ++depth;
+                        if ((uint32_t)lane == depth) { mine = node; mvis = pvis; mval = pval; }
+                        if (depth >= 63) break;
+                    }
+                    float x = 0.0f;
+                    bool fresh = false;
+                    if (mt & kMetaTerminal) x = ((mt & kMetaWinnerPlus) ? 1 : -1) == root_player ? 1.0f : -1.0f;
+                    else if (at_hand(ncr)) x = ncv;
+                    else if (!(mt & kDrained) && node != demanded) fresh = __ballot((uint32_t)lane < ncand && my_cand == node) == 0ull;
+                    if (fresh) { if ((uint32_t)lane == ncand) my_cand = node; if (lane == 0) wl[nw + ncand] = node; ++ncand; fruitless = 0; } else ++fruitless;
+                    r_vis += 1.0f;
+                    if (lane == j0) { c_vis += 1.0f; c_val += x; }
+                    if (lane >= 2 && (uint32_t)lane <= depth) { vvis[mine] = mvis + 1.0f; vval[mine] = mval + x; }
+                    __builtin_amdgcn_wave_barrier();
+                    FR_COUNT(11, 1);
+                }
+            } else
             for (uint32_t step = 0; step < steps_max && ncand < want && fruitless < 8; ++step) {
                 uint32_t node = 0, depth = 0, mine = lane == 0 ? 0u : kNone, mt = 0;
                 for (;;) {
@@ -1541,6 +1657,12 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
 #ifdef DIEE_TAIL_STAMPS
     if (threadIdx.x == 0) atomicMax(&g_free_stamps[10], __builtin_readcyclecounter() - fr_t0_);
 #endif
+}
+
+// before round 0: whether the root expansion's selection (iteration 0's) was a real one, per game, where k_free's batch-first slots read it
+__global__ __launch_bounds__(256) void k_free_first_sel(const uint32_t* __restrict__ sel, uint32_t* __restrict__ first_sel, uint32_t n) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g < n) first_sel[g] = sel[g] == kNone ? kNone : 0u;
 }
 
 // The rows of launch q: every demanded leaf, then the other wishes rank by rank (every game's first candidate, then every game's second ...; the
@@ -2009,6 +2131,7 @@ void launch_free(hipStream_t st, const Tree& T, const Slots& S, const Segs& G, u
         (void)hipFuncSetAttribute((const void*)k_free, hipFuncAttributeMaxDynamicSharedMemorySize, (int)free_lds_bytes(kTailLdsNodes));
         attr_set[dev & 15] = true;
     }
+    if (q == 0) hipLaunchKernelGGL(k_free_first_sel, dim3((n + 255u) / 256u), dim3(256), 0, st, S.sel, F.first_sel, n);
     hipLaunchKernelGGL(k_free, dim3(n), dim3(64), free_lds_bytes(F.lds_nodes), st, T, S, G, n, P, c, FreeArgs{F, q});
     hipLaunchKernelGGL(k_free_pack, dim3(1), dim3(1024), 0, st, F, n, T.node_cap, q, T.state);
 }

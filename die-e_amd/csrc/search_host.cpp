@@ -408,7 +408,7 @@ Free free_view(Engine& e, SearchBufs& B, const diee_mcts_cfg& cfg, uint32_t n) {
                 std::max<uint32_t>(n <= kTailRowsMax ? 2u * e.opt.free_iter_cap : e.opt.free_iter_cap, 1u)};
 }
 
-// The iterations of one move-step's search for 257 ... 928 live games, behind the root expansion (k_expand has selected every game's leaf
+// The iterations of one move-step's search for free_min_games ... free_max_games (17 ... 800) live games, behind the root expansion (k_expand has selected every game's leaf
 // for iteration 0): round 0 = { k_free, k_free_pack }, then rounds { tower launch q over the rows granted, k_free, k_free_pack }.  The game
 // furthest behind completes an iteration in nearly every round (not where its evaluation aged out of the ring or a flag word of another game is
 // still missing), so about `iterations` + 1 rounds suffice at worst -- and about 0.91 * n / rows of that do; the bound is F.launches (free_view).
@@ -500,14 +500,14 @@ void mcts_run(Engine& e, uint32_t n, uint32_t n_segs, const diee_mcts_cfg& cfg, 
     const SearchParams P{cfg.dir_eps, quirks};
     // one MCTS kernel per network evaluation: expand + backpropagate iteration it, then select for it+1
     launch_expand(st, T, S, G, n, kRootIteration, P, cfg.iterations ? 0u : kNoNextIteration, cfg.c, grown, xv);
-    if (free_possible(e, n, cfg)) {                                  // 129 ... 768 live games: every game on its own iteration counter
+    if (free_possible(e, n, cfg)) {                                  // 17 ... 800 live games: every game on its own iteration counter
         S.slot_row = nullptr;
         free_run(e, n, T, S, G, cfg, P);
         launch_reduce_counters(st, S, G, B.step_log.p, std::min(B.cur_step, kStepLog - 1));
         HIPCHK(hipGetLastError());
         return;
     }
-    if (tail_possible(e, n, cfg)) {                                  // <= 96 live games: the games in lockstep inside one launch
+    if (tail_possible(e, n, cfg)) {                                  // <= 16 live games: the games in lockstep inside one launch
         S.slot_row = nullptr;
         tail_run(e, n, T, S, G, cfg, P);
         launch_reduce_counters(st, S, G, B.step_log.p, std::min(B.cur_step, kStepLog - 1));

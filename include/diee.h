@@ -129,7 +129,7 @@ typedef struct {
     double   band_seconds[9];
     uint64_t band_launches[9]; /* sampled evaluations                                                                              */
     double   band_flops[9];
-    /* the tail of a batch (<= spec_max_games = 96 and 129 ... spec_fused_games = 256 live games; option spec_eval): search iterations run by the looping tree kernel, the network launches
+    /* the tail of a batch (<= 16 live games as dispatched: below free_min_games = 17; option spec_eval): search iterations run by the looping tree kernel, the network launches
      * they needed (one per iteration without it), and the rows those launches evaluated on speculation (all batches of the call,
      * reported with batch 0) */
     uint64_t tail_iterations;  /* (round 6: the iterations, launches and speculative rows of the free-running search at 17 ... 800 live games count here too) */
