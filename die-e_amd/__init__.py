@@ -46,7 +46,7 @@ assert TTT_STATE.itemsize == 32
 EXPORTS = [
     "diee_create", "diee_destroy", "diee_last_error", "diee_version", "diee_set_option", "diee_get_option", "diee_device_pci_bus_id", "diee_weights_count",
     "diee_random_weights", "diee_load_weights", "diee_nn_forward", "diee_mcts_batch", "diee_self_play",
-    "diee_self_play_multi", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
+    "diee_self_play_multi", "diee_self_play_refill", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
     "diee_train_conv3x3", "diee_train_im2col3x3",
     "diee_train_scratch_floats", "diee_train_bn_relu_fwd", "diee_train_bn_relu_bwd", "diee_train_colsum",
     "diee_train_set_bn_coop", "diee_train_bn_coop_timeouts",
@@ -151,6 +151,7 @@ def load_library(path=None):
     L.diee_mcts_batch.restype = C.c_int
     L.diee_self_play.argtypes = [vp, u32, u32, vp, f32, u64, u32, u32, vp, vp]; L.diee_self_play.restype = C.c_int
     L.diee_self_play_multi.argtypes = [vp, vp, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_multi.restype = C.c_int
+    L.diee_self_play_refill.argtypes = [vp, vp, u32, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_refill.restype = C.c_int
     L.diee_set_invariant_nn.argtypes = [vp, C.c_int]; L.diee_set_invariant_nn.restype = C.c_int
     L.diee_train_pack_conv3x3.argtypes = [vp, vp, C.c_int, vp]; L.diee_train_pack_conv3x3.restype = C.c_int
     L.diee_train_pack_conv3x3_multi.argtypes = [C.POINTER(vp), C.c_int, vp, vp]; L.diee_train_pack_conv3x3_multi.restype = C.c_int
@@ -452,8 +453,11 @@ class Engine:
         flags = (FLAG_REF_QUIRKS if ref_quirks else 0) | (FLAG_INVARIANT_NN if invariant_nn else 0)
         self._chk(self._L.diee_self_play_multi(self._h, C.byref(bt), K, C.byref(cfg), temperature, flags, max_steps,
                                                C.byref(frs) if fetch else None, C.byref(sts)))
+        return self._take_batches(frs, sts, fetch, copy)
+
+    def _take_batches(self, frs, sts, fetch, copy):
         outs = []
-        for k in range(K):
+        for k in range(len(sts)):
             out = {"stats": sts[k].as_dict()}
             if fetch:
                 self._take_fragments(frs[k], out, copy)
@@ -461,6 +465,18 @@ class Engine:
                     out["_keep"] = frs            # (the array of diee_fragments the free closures point into)
             outs.append(out)
         return outs
+
+    def self_play_refill(self, batches, width, cfg, temperature=1.25, max_steps=0, fetch=True, invariant_nn=False, copy=True):
+        """the games of `batches` with slot refill (diee_self_play_refill, opt-in: not the reference's loop): at most `width` in
+        flight, a retired game's slot taken by the next unstarted game; always without the quirks.  Per batch the records of
+        self_play_parallel(..., ref_quirks=False) up to their order (include/diee.h) -> list of per-batch dicts"""
+        K = len(batches)
+        bt = (Batch * K)(*[Batch(int(n), int(f), int(s)) for n, f, s in batches])
+        frs = (Fragments * K)(); sts = (Stats * K)()
+        flags = FLAG_INVARIANT_NN if invariant_nn else 0
+        self._chk(self._L.diee_self_play_refill(self._h, C.byref(bt), K, int(width), C.byref(cfg), temperature, flags, max_steps,
+                                                C.byref(frs) if fetch else None, C.byref(sts)))
+        return self._take_batches(frs, sts, fetch, copy)
 
 
 # ---- LearnableGame for TicTacToe (src/tictactoe/mod.rs), host functions of the C ABI -------------------------------------

@@ -245,6 +245,18 @@ class AlphaZero:
         for _ in range(K):
             self.calls += 1
             batches.append((n, self.rank * n, self.seed + 0x9E3779B1 * self.calls))
+        # opt-in (DIEE_REFILL_WIDTH=n; NOT the reference's loop, alpha_parallel.rs:129): the K calls' games through n slots in one
+        # diee_self_play_refill call -- a retired game's slot goes to the next unstarted game.  Always without the quirks (Q14 couples the
+        # slots of a reference call), so the records are those of K calls with ref_quirks off, in another order.  What the call holds in HBM
+        # goes by the width, so there is nothing to group by DIEE_PIPELINE_GB; a call still takes at most 64 batches.
+        width = int(os.environ.get("DIEE_REFILL_WIDTH", "0") or 0)
+        if width > 0:
+            self.log(f"[self-play] DIEE_REFILL_WIDTH={width}: {K} x {n} games with at most {width} in flight (slot refill), ref_quirks off")
+            outs = []
+            for g0 in range(0, K, 64):
+                outs += self.engine.self_play_refill(batches[g0:g0 + 64], width, self.mcts_config, self.config.temperature)
+            self.last_stats = outs[-1]["stats"]
+            return [{"outcome": o["outcome"], "ps": o["ps"], "state": o["state"]} for o in outs]
         # a call takes at most 64 batches (kMaxSegments) and its fragment arena grows with the batches in flight
         # (games x (round_limit + 2) x 6 KB: 2.5 GB per 1024-game batch): groups within both limits, one call per group
         per_batch = n * (self.mcts_config.round_limit + 2) * (self.game.actions + self.game.planes) * 4 + n * (self.mcts_config.iterations + 1) * 128 * 56

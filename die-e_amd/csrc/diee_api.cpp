@@ -254,6 +254,15 @@ diee_status diee_self_play_multi(diee_ctx* c, const diee_batch* batches, uint32_
     API_END(c)
 }
 
+diee_status diee_self_play_refill(diee_ctx* c, const diee_batch* batches, uint32_t n_batches, uint32_t width,
+                                  const diee_mcts_cfg* cfg, float temperature, uint32_t flags, uint32_t max_steps,
+                                  diee_fragments* outs, diee_stats* stats) {
+    API_BEGIN(c)
+    if (!cfg || !batches) throw EngineError(DIEE_ERR_ARG, "bad arguments");
+    bg(c)->self_play_refill(batches, n_batches, width, cfg, temperature, flags, max_steps, outs, stats);
+    API_END(c)
+}
+
 diee_status diee_dev_conv_bench(diee_ctx* c, int G, int variant, int reps, float* us_mode0, float* us_mode1,
                                 float* us_forward) {
     API_BEGIN(c)

@@ -45,6 +45,7 @@ const OptEntry kOptions[] = {
     {"test_starve_at", &Options::test_starve_at, nullptr, nullptr}, {"test_tail_skip", &Options::test_tail_skip, nullptr, nullptr},
     {"pinned_pool_mb", nullptr, nullptr, nullptr},          // process-wide: the cap of the pool of page-locked output blocks (search_host.cpp)
 };
+const char kRefillAreas[] = "refill_record_areas";          // read-only: record areas the last diee_self_play_refill allocated
 const OptEntry* find_option(const std::string& key) {
     for (const auto& e : kOptions) if (key == e.key) return &e;
     return nullptr;
@@ -72,6 +73,7 @@ bool table_ok(const std::string& v) {
 }  // namespace
 
 void Engine::set_option(const std::string& key, const std::string& value) {
+    if (key == kRefillAreas) throw EngineError(DIEE_ERR_ARG, "option " + key + " is read-only");
     const OptEntry* e = find_option(key);
     if (!e) throw EngineError(DIEE_ERR_ARG, "unknown option `" + key + "`");
     if (!e->s && !e->i && !e->u) {                          // pinned_pool_mb
@@ -92,6 +94,7 @@ void Engine::set_option(const std::string& key, const std::string& value) {
 }
 
 std::string Engine::get_option(const std::string& key) const {
+    if (key == kRefillAreas) return std::to_string(refill_areas);
     const OptEntry* e = find_option(key);
     if (!e) throw EngineError(DIEE_ERR_ARG, "unknown option `" + key + "`");
     if (!e->s && !e->i && !e->u) return std::to_string(pinned_pool_cap_mb());

@@ -117,6 +117,9 @@ public:
                    uint64_t seed, uint32_t flags, uint32_t max_steps, diee_fragments* out, diee_stats* stats);
     void self_play_multi(const diee_batch* batches, uint32_t n_batches, const diee_mcts_cfg* cfg, float temperature,
                          uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats);
+    void self_play_refill(const diee_batch* batches, uint32_t n_batches, uint32_t width, const diee_mcts_cfg* cfg, float temperature,
+                          uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats);
+    uint32_t refill_areas = 0;       // record areas the last self_play_refill allocated (read-only option refill_record_areas)
 
     int device;
     hipStream_t stream = nullptr;
@@ -139,6 +142,10 @@ public:
     void apply_options();                                                  // opt -> NetWeights (after load_weights, after set_option)
 
     DevBuf<uint8_t> tmp_a, tmp_b, tmp_c, tmp_d, tmp_e;
+private:
+    void self_play_run(const diee_batch* batches, uint32_t n_batches, uint32_t width, const diee_mcts_cfg* cfg, float temperature,
+                       uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats);
+public:
     DevBuf<uint32_t> flags_dev;      // [0] capacity-overflow flag
     NetWeights* net = nullptr;
     SearchBufs* search = nullptr;

@@ -114,6 +114,10 @@ void launch_init_games(hipStream_t st, const Games& Gm, const Segs& G, uint32_t 
 void launch_gather_roots(hipStream_t st, const Games& Gm, const Slots& S, const Segs& G, uint32_t n_live);
 void launch_play_move(hipStream_t st, const Tree& T, const Games& Gm, const Segs& G, uint32_t n_live, uint32_t step, const PlayParams& P);
 void launch_compact_live(hipStream_t st, const Games& Gm, uint32_t n_live, uint32_t n_segs, uint32_t* n_live_out);
+// slot refill: the areas of the step's retired games go back on the stack fr = { count, stack[fr_cap] } (before the compaction), then games
+// next, next + 1, ... join the live list until `width` are in flight (behind it; n_live_out[0] = games alive)
+void launch_refill_release(hipStream_t st, const Games& Gm, uint32_t n_live, uint32_t* fr, uint32_t fr_cap);
+void launch_refill_admit(hipStream_t st, const Games& Gm, const uint32_t* n_live_out, uint32_t width, uint32_t next, uint32_t total, uint32_t* fr);
 // output delivery of a move-step: the step's flushes in the reference's order (summary: DeliverSummary), then ranges of their rows
 void launch_deliver_scan(hipStream_t st, const Games& Gm, const Segs& G, uint32_t n_live, uint32_t step, DeliverEvent* ev, uint32_t* summary);
 void launch_deliver_copy(hipStream_t st, const Games& Gm, const Segs& G, const DeliverEvent* ev, uint32_t n_ev, uint32_t r0, uint32_t r1,

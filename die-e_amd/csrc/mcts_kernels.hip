@@ -468,7 +468,7 @@ __device__ __forceinline__ void expand_body(const Tree& T, const Slots& S, const
                 const uint32_t code = ((q & 2) ? pre_codes.y : pre_codes.x) >> (16 * (q & 1)) & 0xFFFFu;
                 float p = softmax_prob(sc.lgs[code], smM, smInv);
                 if (root) {                                  // apply_dirichlet: (1-eps)*P + eps*noise
-                    const float x = om * p, y = P.dir_eps * S.noise[(size_t)seg * 1352 + code];
+                    const float x = om * p, y = P.dir_eps * S.noise[((size_t)(S.noise_segs ? rnd * S.noise_segs : 0u) + seg) * 1352 + code];
                     p = x + y;
                 }
                 sc.raw[j] = p;
@@ -523,7 +523,7 @@ __device__ __forceinline__ void expand_body(const Tree& T, const Slots& S, const
             const uint32_t code = bg_encode_dev(r0, r1, play);
             float p = softmax_prob(lgs[code], smM, smInv);
             if (root) {                                      // apply_dirichlet: (1-eps)*P + eps*noise
-                const float x = om * p, y = P.dir_eps * S.noise[(size_t)seg * 1352 + code];
+                const float x = om * p, y = P.dir_eps * S.noise[((size_t)(S.noise_segs ? rnd * S.noise_segs : 0u) + seg) * 1352 + code];
                 p = x + y;
                 if (bg_decode_dev(r0, r1, player, code) != play) atomicAdd(&S.slot_cnt[slot * SC_COUNT + SC_ILLEGAL], 1u);
             }
@@ -1953,7 +1953,7 @@ __global__ __launch_bounds__(64) void k_play_move(Tree T, Games Gm, Segs G, uint
     const uint32_t code = (uint32_t)(pick >= 0 ? pick : last_nz);        // (uniform: every lane ran the same chain)
     // MemoryFragment{outcome: player, ps, state} (:195-199)
     const uint32_t nf = Gm.nfrags[g];
-    const size_t fi = (size_t)g * Gm.frag_cap + nf;
+    const size_t fi = (size_t)(Gm.area ? Gm.area[g] : g) * Gm.frag_cap + nf;
     for (int a = lane; a < 1352; a += 64) Gm.frag_ps[fi * 1352 + a] = row[a];
     for (int t = lane; t < 144; t += 64) Gm.frag_planes[fi * 144 + t] = bg_plane_dev(s, t / 24, t % 24);
     if (lane == 0) {
@@ -2006,6 +2006,53 @@ __global__ __launch_bounds__(1024) void k_compact_live(Games Gm, uint32_t n_live
     }
     if (tid == 0) n_live_out[0] = carry;
     if (tid < (int)n_segs) n_live_out[1 + tid] = per_seg[tid];
+}
+
+// ---- slot refill (diee_self_play_refill) ------------------------------------------------------------------------------------------
+// At most `width` games are in flight; a retired game's slot is taken, in the next move-step, by the next unstarted game.  Every unstarted
+// index is above every live one, so appending keeps the live list ascending (k_gather_roots needs that).  The fragments of a game live in
+// record area Gm.area[g]; fr = { count, stack[width] } holds the areas nobody owns.
+// k_refill_release (one block; behind k_deliver_scan, before k_compact_live drops them from the list): the areas of this step's retired games,
+// in the live list's order
+__global__ __launch_bounds__(1024) void k_refill_release(Games Gm, uint32_t n_live, uint32_t* __restrict__ fr, uint32_t fr_cap) {
+    __shared__ uint32_t wsum[16];
+    __shared__ uint32_t carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) carry = fr[0];
+    __syncthreads();
+    for (uint32_t c0 = 0; c0 < n_live; c0 += 1024) {
+        const uint32_t i = c0 + tid;
+        uint32_t g = 0;
+        bool dead = false;
+        if (i < n_live) { g = Gm.live[i]; dead = Gm.alive[g] == 0; }
+        const unsigned long long bal = __ballot(dead);
+        if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = carry;
+        for (int w = 0; w < wave; ++w) off += wsum[w];
+        const uint32_t pos = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (dead && pos < fr_cap) fr[1 + pos] = Gm.area[g];
+        __syncthreads();
+        if (tid == 0) { uint32_t t = 0; for (int w = 0; w < 16; ++w) t += wsum[w]; carry += t; }
+        __syncthreads();
+    }
+    if (tid == 0) fr[0] = carry < fr_cap ? carry : fr_cap;
+}
+// k_refill_admit (one block; behind k_compact_live, which left the games alive in n_live_out[0]): games next, next + 1, ... join the live list
+// until `width` are in flight or none is left, each on an area off the stack.  The host derives the same count from the same three numbers.
+__global__ __launch_bounds__(1024) void k_refill_admit(Games Gm, const uint32_t* __restrict__ n_live_out, uint32_t width, uint32_t next,
+                                                       uint32_t total, uint32_t* __restrict__ fr) {
+    const uint32_t c = n_live_out[0], fn = fr[0];
+    uint32_t add = width > c ? width - c : 0u;
+    if (add > total - next) add = total - next;
+    if (add > fn) add = fn;                                     // (every game in flight owns one of `width` areas: fn == width - c)
+    __syncthreads();                                            // fr[0] read by all before it changes
+    for (uint32_t i = threadIdx.x; i < add; i += 1024) {
+        const uint32_t g = next + i;
+        Gm.live[c + i] = g;
+        Gm.area[g] = fr[fn - i];                                // stack[fn - 1 - i]
+    }
+    if (threadIdx.x == 0) fr[0] = fn - add;
 }
 
 // ---- output delivery (alpha_parallel.rs:172-180, :215-223: `all_memories.append(...)` in the step a game is removed) ----
@@ -2077,7 +2124,7 @@ __global__ __launch_bounds__(256) void k_deliver_copy(Games Gm, Segs G, const De
         while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (ev[mid].row0 <= r) lo = mid; else hi = mid; }
         const DeliverEvent d = ev[lo];
         const uint32_t fr = r - d.row0;
-        const size_t s = (size_t)d.g * Gm.frag_cap + fr, o = (size_t)(r - r0);
+        const size_t s = (size_t)(Gm.area ? Gm.area[d.g] : d.g) * Gm.frag_cap + fr, o = (size_t)(r - r0);
         for (int a = threadIdx.x; a < 1352 / 4; a += 256)
             reinterpret_cast<float4*>(out.ps + o * 1352)[a] = reinterpret_cast<const float4*>(Gm.frag_ps + s * 1352)[a];
         if (threadIdx.x < 144 / 4)
@@ -2156,6 +2203,12 @@ void launch_play_move(hipStream_t st, const Tree& T, const Games& Gm, const Segs
 }
 void launch_compact_live(hipStream_t st, const Games& Gm, uint32_t n_live, uint32_t n_segs, uint32_t* n_live_out) {
     hipLaunchKernelGGL(k_compact_live, dim3(1), dim3(1024), 0, st, Gm, n_live, n_segs, n_live_out);
+}
+void launch_refill_release(hipStream_t st, const Games& Gm, uint32_t n_live, uint32_t* fr, uint32_t fr_cap) {
+    hipLaunchKernelGGL(k_refill_release, dim3(1), dim3(1024), 0, st, Gm, n_live, fr, fr_cap);
+}
+void launch_refill_admit(hipStream_t st, const Games& Gm, const uint32_t* n_live_out, uint32_t width, uint32_t next, uint32_t total, uint32_t* fr) {
+    hipLaunchKernelGGL(k_refill_admit, dim3(1), dim3(1024), 0, st, Gm, n_live_out, width, next, total, fr);
 }
 void launch_deliver_scan(hipStream_t st, const Games& Gm, const Segs& G, uint32_t n_live, uint32_t step, DeliverEvent* ev, uint32_t* summary) {
     hipLaunchKernelGGL(k_deliver_scan, dim3(1), dim3(1024), 0, st, Gm, G, n_live, step, ev, summary);

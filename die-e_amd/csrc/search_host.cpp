@@ -65,7 +65,12 @@ struct SearchBufs {
     DevBuf<uint8_t> alive, gseg;
     DevBuf<int8_t> winner, frag_player;
     DevBuf<float> frag_ps, frag_planes;
-    uint32_t game_cap = 0, frag_cap = 0;
+    uint32_t game_cap = 0, area_cap = 0, frag_cap = 0;         // games (the small per-game words), record areas and fragments per area (the arena)
+    // slot refill (self_play_refill): the record area of every game, the stack of free areas { count, stack[width] }, and the Dirichlet
+    // samples of the call so far, [move-step][batch][1352] (Slots::noise_segs)
+    DevBuf<uint32_t> rf_area, rf_free;
+    DevBuf<float> noise_tab;
+    uint32_t noise_rows = 0;                                   // move-steps noise_tab holds in this call; 0: not a refill call
     // output delivery: this step's flushes (double-buffered: the copy stream reads step s's list while step s + 1's is written),
     // one staging buffer (the copy stream runs gather -> copies out -> next gather in order), the stream and its guards
     DevBuf<DeliverEvent> dl_events[2];
@@ -236,7 +241,7 @@ Slots slots_view(Engine& e, SearchBufs& B) {
     const NetHeads H = nn_heads(e, (int)B.slot_cap);      // the network's output buffers, sized for every slot
     return Slots{B.roots.p, B.eval_states.p, B.game_id.p, B.round.p, B.seg.p, B.leaf.p, B.sel.p, B.sel_value.p, B.leaf_term.p,
                  nullptr, H.logits, H.hv, H.wv, B.noise.p, B.root_value0.p, B.iter_flags.p, B.counters.p, B.slot_cnt.p, e.flags_dev.p,
-                 B.leaf_meta.p, B.path.p, B.path_len.p, B.grow_k.p, B.grow_code.p, std::min<uint32_t>(e.opt.path_cap, kPathCap)};
+                 B.leaf_meta.p, B.path.p, B.path_len.p, B.grow_k.p, B.grow_code.p, std::min<uint32_t>(e.opt.path_cap, kPathCap), 0u};
 }
 Segs segs_view(SearchBufs& B, uint32_t n_segs) {
     return Segs{B.seg_seed.p, B.seg_first_id.p, B.seg_game0.p, B.seg_slots.p, B.seg_slots.p + kMaxSegments, n_segs, B.iter_cap};
@@ -475,8 +480,13 @@ void mcts_run(Engine& e, uint32_t n, uint32_t n_segs, const diee_mcts_cfg& cfg, 
     // slots whose selected leaf was terminal need no network row: above 256 live games only the others are evaluated
     const NnRows rows{B.leaf_term.p, B.row_slot.p, B.slot_row.p, B.n_rows.p};
     HIPCHK(hipMemsetAsync(B.iter_flags.p, 0, sizeof(uint32_t) * 2 * (size_t)B.iter_cap * n_segs, st));
-    HIPCHK(hipMemcpyAsync(B.noise.p, B.noise_host + (size_t)buf * kMaxSegments * 1352, sizeof(float) * 1352 * n_segs,
-                          hipMemcpyHostToDevice, st));
+    // slot refill: this move-step's samples join the table of the call's, and a root reads the row of its own round (no game is past
+    // round noise_rows - 1, so later move-steps add nothing)
+    const bool noise_by_round = B.noise_rows != 0;
+    if (noise_by_round) { S.noise = B.noise_tab.p; S.noise_segs = n_segs; }
+    if (!noise_by_round || B.cur_step < B.noise_rows)
+        HIPCHK(hipMemcpyAsync(noise_by_round ? B.noise_tab.p + (size_t)B.cur_step * n_segs * 1352 : B.noise.p, B.noise_host + (size_t)buf * kMaxSegments * 1352, sizeof(float) * 1352 * n_segs,
+                              hipMemcpyHostToDevice, st));
     launch_init_roots(st, T, S, n);
     // option cl_grow (default on): below 129 boards the evaluation is ONE cluster-tower launch, latency-bound, with CUs to spare while
     // fewer than ~28 games live (the tail of a batch: 130 of its 364 move-steps): the launch takes the growth along on extra
@@ -599,6 +609,7 @@ void Engine::mcts_batch(const diee_bg_state* roots, uint32_t n, const diee_mcts_
     reserve_search(*this, n, cfg->iterations);
     nn_reserve(*this, (int)n);
     SearchBufs& B = *search;
+    B.noise_rows = 0;
     const InvariantScope inv(*this, flags);
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint32_t> ids(n), rds(n);
@@ -650,6 +661,25 @@ void Engine::self_play(uint32_t n_games, uint32_t first_game_id, const diee_mcts
 // produces depends on the other batches only through the network kernel its rows are evaluated by.
 void Engine::self_play_multi(const diee_batch* batches, uint32_t n_batches, const diee_mcts_cfg* cfg, float temperature,
                              uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats) {
+    self_play_run(batches, n_batches, 0u, cfg, temperature, flags, max_steps, outs, stats);
+}
+
+// Slot refill (opt-in; the reference's loop, alpha_parallel.rs:129, plays the games a call started with and nothing else): at most `width`
+// games of the call are in flight, and the slot of a game retired in move-step s is taken in s + 1 by the next unstarted game (batch-major,
+// ascending game id).  Without the quirks nothing couples the games of a batch but the Dirichlet sample of a move-step, and in a reference
+// call every live game's round IS the move-step: a game admitted late reads the sample of its own round (Slots::noise_segs), its dice and
+// sampling keys are (batch seed, game id, round) anyway, so its records are those of a plain call of its batch.  What the call holds in HBM
+// goes by `width`: slots, trees, network rows and the record areas of the games in flight (Games::area).
+void Engine::self_play_refill(const diee_batch* batches, uint32_t n_batches, uint32_t width, const diee_mcts_cfg* cfg, float temperature,
+                              uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats) {
+    if (flags & DIEE_FLAG_REF_QUIRKS) throw EngineError(DIEE_ERR_ARG, "slot refill needs DIEE_FLAG_REF_QUIRKS off (Q14 couples the slots of a reference call)");
+    if (width == 0) throw EngineError(DIEE_ERR_ARG, "width must be >= 1");
+    self_play_run(batches, n_batches, width, cfg, temperature, flags, max_steps, outs, stats);
+}
+
+// width == 0: every game of the call starts at move-step 0 (self_play_multi); else slot refill
+void Engine::self_play_run(const diee_batch* batches, uint32_t n_batches, uint32_t width, const diee_mcts_cfg* cfg, float temperature,
+                           uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats) {
     HIPCHK(hipSetDevice(device));
     if (!net || !net->loaded) throw EngineError(DIEE_ERR_NO_WEIGHTS, "diee_load_weights has not been called");
     if (outs) memset(outs, 0, sizeof(diee_fragments) * n_batches);
@@ -665,23 +695,40 @@ void Engine::self_play_multi(const diee_batch* batches, uint32_t n_batches, cons
     }
     if (total_games > (1u << 22)) throw EngineError(DIEE_ERR_ARG, "too many games in flight");
     const uint32_t n_games = (uint32_t)total_games;
-    reserve_search(*this, n_games, cfg->iterations);
-    nn_reserve(*this, (int)n_games);
+    const bool refill = width != 0;
+    const uint32_t n_slots = refill ? std::min(width, n_games) : n_games;      // games in flight at most: slots, trees, network rows, record areas
+    // slot refill: the Dirichlet samples of move-steps 0 ... round_limit (no game is searched in a later round), fewer under max_steps
+    const uint64_t noise_rows = refill ? std::min<uint64_t>(cfg->round_limit, max_steps ? max_steps - 1 : 0xFFFFFFFFu) + 1 : 0;
+    if (noise_rows * n_batches * 1352 * sizeof(float) > ((uint64_t)8 << 30))
+        throw EngineError(DIEE_ERR_ARG, "slot refill keeps one Dirichlet sample per batch and round: round_limit x batches is too large");
+    reserve_search(*this, n_slots, cfg->iterations);
+    nn_reserve(*this, (int)n_slots);
     SearchBufs& B = *search;
+    B.noise_rows = (uint32_t)noise_rows;
+    struct NoiseScope { SearchBufs& B; ~NoiseScope() { B.noise_rows = 0; } } noise_scope{B};
     const InvariantScope inv(*this, flags);
     const uint32_t frag_cap = cfg->round_limit + 2;
-    if (n_games > B.game_cap || frag_cap > B.frag_cap) {
-        const uint32_t gc = std::max(n_games, B.game_cap), fc = std::max(frag_cap, B.frag_cap);
+    if (n_games > B.game_cap) {
+        const uint32_t gc = n_games;
         B.gstate.ensure(gc); B.rounds.ensure(gc); B.nfrags.ensure(gc); B.alive.ensure(gc); B.winner.ensure(gc);
         B.ev_a_count.ensure(gc); B.ev_a_step.ensure(gc); B.ev_b_count.ensure(gc); B.ev_b_step.ensure(gc);
         B.live.ensure(gc); B.gseg.ensure(gc);
-        B.frag_ps.ensure((size_t)gc * fc * 1352); B.frag_planes.ensure((size_t)gc * fc * 144);
-        B.frag_player.ensure((size_t)gc * fc);
-        B.game_cap = gc; B.frag_cap = fc;
+        B.game_cap = gc;
+    }
+    if (n_slots > B.area_cap || frag_cap > B.frag_cap) {
+        const uint32_t ac = std::max(n_slots, B.area_cap), fc = std::max(frag_cap, B.frag_cap);
+        B.frag_ps.ensure((size_t)ac * fc * 1352); B.frag_planes.ensure((size_t)ac * fc * 144);
+        B.frag_player.ensure((size_t)ac * fc);
+        B.area_cap = ac; B.frag_cap = fc;
+    }
+    if (refill) {
+        B.rf_area.ensure(n_games); B.rf_free.ensure((size_t)n_slots + 1);
+        B.noise_tab.ensure((size_t)noise_rows * n_batches * 1352);
+        refill_areas = n_slots;
     }
     const Games Gm{B.gstate.p, B.rounds.p, B.nfrags.p, B.alive.p, B.winner.p, B.ev_a_count.p, B.ev_a_step.p,
                    B.ev_b_count.p, B.ev_b_step.p, B.live.p, B.gseg.p, B.frag_ps.p, B.frag_planes.p, B.frag_player.p,
-                   B.frag_cap, B.counters.p};
+                   B.frag_cap, B.counters.p, refill ? B.rf_area.p : nullptr};
     const Tree T = tree_view(B);
     const Slots S = slots_view(*this, B);
     const Segs G = segs_view(B, n_batches);
@@ -697,7 +744,7 @@ void Engine::self_play_multi(const diee_batch* batches, uint32_t n_batches, cons
     const bool deliver = outs != nullptr;
     std::vector<FragBufs> fb(deliver ? n_batches : 0);
     std::vector<uint64_t> frag_total(n_batches, 0);
-    for (auto& ev : B.dl_events) ev.ensure((size_t)2 * n_games);
+    for (auto& ev : B.dl_events) ev.ensure((size_t)2 * n_slots);
     B.ev_copy_armed[0] = B.ev_copy_armed[1] = false;
     const uint32_t stage_rows = std::max<uint32_t>(opt.deliver_stage_rows, 1);
     double deliver_secs = 0.0;
@@ -754,14 +801,26 @@ void Engine::self_play_multi(const diee_batch* batches, uint32_t n_batches, cons
     HIPCHK(hipMemsetAsync(B.step_log.p, 0, sizeof(unsigned long long) * 2 * kStepLog, stream));
     nn_reset_timing(*this);
     launch_init_games(stream, Gm, G, n_games);
+    std::vector<uint32_t> area0;                                        // slot refill: the first n_slots games are in flight, game g on area g; no area is free
+    if (refill) {
+        area0.resize(n_slots);
+        for (uint32_t g = 0; g < n_slots; ++g) area0[g] = g;
+        h2d(B.rf_area.p, area0.data(), area0.size());
+        HIPCHK(hipMemsetAsync(B.rf_free.p, 0, sizeof(uint32_t), stream));
+    }
     draw_noise(B, 0, bt, 0, cfg->dir_alpha);
     sync();
     // ---- timed region: every input is resident in HBM ----
     const auto t0 = std::chrono::steady_clock::now();
-    uint32_t n_live = n_games, step = 0;
+    uint32_t n_live = n_slots, step = 0;
+    uint32_t next_game = n_slots;                                       // slot refill: the next unstarted game
     std::vector<uint32_t> steps_of(n_batches, 0);                       // move-steps each batch took part in
     std::vector<uint32_t> live_of(n_batches);
-    for (uint32_t k = 0; k < n_batches; ++k) live_of[k] = bt[k].n_games;
+    auto started_of = [&](uint32_t k, uint32_t lo, uint32_t hi) {       // games of batch k among games [lo, hi)
+        const uint32_t a = std::max(lo, game0[k]), b = std::min(hi, game0[k] + bt[k].n_games);
+        return b > a ? b - a : 0u;
+    };
+    for (uint32_t k = 0; k < n_batches; ++k) live_of[k] = started_of(k, 0, n_slots);
     const bool trace_steps = opt.trace_steps != 0;                        // development: batch size of every move-step
     while (n_live > 0 && (max_steps == 0 || step < max_steps)) {       // alpha_parallel.rs:129
         if (trace_steps) fprintf(stderr, "[diee] move-step %u: %u games alive\n", step, n_live);
@@ -774,21 +833,31 @@ void Engine::self_play_multi(const diee_batch* batches, uint32_t n_batches, cons
         mcts_run(*this, n_live, n_batches, *cfg, buf, flags);           // :146
         // while the GPU searches: the next move-step's Dirichlet samples (the only host arithmetic of a move-step) and the
         // previous move-step's records (enqueued behind this step's search so that the search never waits for the host)
-        draw_noise(B, buf ^ 1, bt, step + 1, cfg->dir_alpha);
+        if (!refill || step + 1 < B.noise_rows) draw_noise(B, buf ^ 1, bt, step + 1, cfg->dir_alpha);
         deliver_pending();
         if (cluster_starved(*this)) {                                   // rare: repeat this move-step's search, per-layer kernels
             HIPCHK(hipMemcpyAsync(B.counters.p, B.counters_bak.p, sizeof(unsigned long long) * CNT_COUNT * n_batches, hipMemcpyDeviceToDevice, stream));
             mcts_run(*this, n_live, n_batches, *cfg, buf, flags);
         }
+        // slot refill: the areas of the games retired in step - 1 went to the games admitted behind them, whose first records are written now --
+        // behind the gather of the retired games' records (deliver_pending above, on the copy stream).  The search has just covered that wait.
+        if (refill && B.ev_copy_armed[buf ^ 1]) { HIPCHK(hipStreamWaitEvent(stream, B.ev_copy[buf ^ 1], 0)); B.ev_copy_armed[buf ^ 1] = false; }
         launch_play_move(stream, T, Gm, G, n_live, step, PP);           // :164-224
         if (B.ev_copy_armed[buf]) { HIPCHK(hipStreamWaitEvent(stream, B.ev_copy[buf], 0)); B.ev_copy_armed[buf] = false; }   // (step - 2's list has been read)
         launch_deliver_scan(stream, Gm, G, n_live, step, B.dl_events[buf].p, B.n_live_dev.p);
+        if (refill) launch_refill_release(stream, Gm, n_live, B.rf_free.p, n_slots);
         launch_compact_live(stream, Gm, n_live, n_batches, B.n_live_dev.p);   // :226-228
+        if (refill) launch_refill_admit(stream, Gm, B.n_live_dev.p, n_slots, next_game, n_games, B.rf_free.p);
         HIPCHK(hipGetLastError());
         d2h(B.live_host, B.n_live_dev.p, (size_t)1 + 4 * n_batches);
         sync();
         n_live = B.live_host[0];
         for (uint32_t k = 0; k < n_batches; ++k) live_of[k] = B.live_host[1 + k];
+        if (refill) {                                                   // what k_refill_admit appended to the live list
+            const uint32_t add = std::min(n_slots - n_live, n_games - next_game);
+            for (uint32_t k = 0; k < n_batches; ++k) live_of[k] += started_of(k, next_game, next_game + add);
+            n_live += add; next_game += add;
+        }
         pending.assign(B.live_host, B.live_host + 1 + 4 * n_batches);
         pending_buf = buf;
         ++step;

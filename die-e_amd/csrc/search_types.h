@@ -62,7 +62,8 @@ struct Slots {
     const float* logits;    // [slots][1352] policy logits of this iteration's evaluation (nn_host's buffers)
     const float* hv;        // [slots][72] value features
     const float* wv;        // [73] value FC
-    float* noise;           // [segs][1352] Dirichlet sample of this move-step, one per batch (noise.rs:27-34)
+    float* noise;           // [segs][1352] Dirichlet sample of this move-step, one per batch (noise.rs:27-34); slot refill (noise_segs != 0):
+                            // [move-step][segs][1352], a root reads the row of its own game's round
     float* root_value0;     // [segs] NN value of the root in the batch's first slot
     uint32_t* iter_flags;   // [segs][iter_cap][2] any_selected, stale-initial count per iteration
     unsigned long long* counters;  // [segs][CNT_COUNT] totals (written by k_reduce_counters / single lanes only)
@@ -75,6 +76,8 @@ struct Slots {
     uint32_t* grow_k;       // [slots] children the growth workgroups of a tower launch created for the slot's leaf this iteration (0xFFFFFFFF: none to create / no room)
     uint16_t* grow_code;    // [slots][kMaxPlays] their action codes, child lane + 64 q at [lane * 4 + q]
     uint32_t path_cap;      // depths recorded (<= kPathCap = 64; option path_cap lowers it so that tests reach the parent walk)
+    uint32_t noise_segs;    // 0: every live game of a batch is in the batch's current move-step (noise[seg]); n > 0: slot refill, n batches, the
+                            // games of a batch are in different rounds and a game admitted late needs the sample of ITS round: noise[round * n + seg]
 };
 constexpr int kPathCap = 64;
 
@@ -90,11 +93,13 @@ struct Games {
     uint32_t* ev_b_step;
     uint32_t* live;         // [games] live list (ascending game index, hence batch-major)
     uint8_t* seg;           // [games] batch of the game
-    float* frag_ps;         // [games][frag_cap][1352]
-    float* frag_planes;     // [games][frag_cap][144]
-    int8_t* frag_player;    // [games][frag_cap]
+    float* frag_ps;         // [record areas][frag_cap][1352]
+    float* frag_planes;     // [record areas][frag_cap][144]
+    int8_t* frag_player;    // [record areas][frag_cap]
     uint32_t frag_cap;
     unsigned long long* counters;
+    uint32_t* area;         // [games] record area of the game's fragments; null: the identity (one area per game of the call).  Slot refill
+                            // keeps as many areas as games are in flight and hands a retired game's area to the game that takes its slot
 };
 
 // Output delivery of one move-step (alpha_parallel.rs:172-180, :215-223: a game's memory joins all_memories, relabelled, in

@@ -195,6 +195,8 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *   pinned_pool_mb        MiB of page-locked output blocks the PROCESS keeps for reuse after diee_free_fragments (default 8192;
  *                                 with several ranks per host: what each may retain)
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
+ *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
+ *                                 diee_self_play_refill of this ctx allocated: min(width, games of the call), whatever the call's length
  *   cl_pack, cl_grow, expand2, expand2c, spec_rollout_steps (virtual descents per game and launch, default 24), spec_fused_from, fused_heads, cluster_heads, cluster_init, trace_steps,
  *   trace_dispatch, test_starve_at, test_tail_skip                                                  development / test switches
  * Unknown key or malformed value: DIEE_ERR_ARG.  Not for a tic-tac-toe ctx (DIEE_ERR_UNSUPPORTED). */
@@ -261,6 +263,26 @@ typedef struct {
 diee_status diee_self_play_multi(diee_ctx*, const diee_batch* batches, uint32_t n_batches,
                                  const diee_mcts_cfg* cfg, float temperature, uint32_t flags,
                                  uint32_t max_steps, diee_fragments* outs, diee_stats* stats);
+
+/* ---- level 2 with slot refill (opt-in; NOT what the reference's loop does, alpha_parallel.rs:129: it plays the games a call started
+ * with until the last one ends): the games of batches[0..n_batches) played with at most `width` in flight: a retired game's slot is
+ * taken, in the next move-step, by the next unstarted game (batch-major, ascending game id).  The batch keeps its width for as long as
+ * unstarted games are left instead of ending in a tail of a few live games per batch, and what the call holds in HBM -- trees, network
+ * rows, record areas -- goes by `width`, not by the games of the call (a retired game's record area is handed to the game that takes
+ * its slot once its records have been gathered for delivery).
+ *   DIEE_FLAG_REF_QUIRKS in flags: DIEE_ERR_ARG (Q14 couples the slots of a reference call: there is nothing to be equal to);
+ *   width == 0: DIEE_ERR_ARG; a tic-tac-toe ctx: DIEE_ERR_UNSUPPORTED; DIEE_FLAG_INVARIANT_NN as elsewhere.
+ * Without the quirks the games of a batch share only the Dirichlet sample of a move-step, and in a reference call a live game's round is
+ * the move-step: a game admitted late is given the sample of its own round.  So for each batch the MULTISET of records equals
+ * diee_self_play(batches[b], flags) -- byte for byte under DIEE_FLAG_INVARIANT_NN, otherwise up to which tower kernel evaluated a row (as
+ * for diee_self_play_multi).  ROW ORDER: a game's records are contiguous and in play order; games appear by the move-step OF THIS CALL in
+ * which they retired, then by game id, a round-limit flush before a win flush.  With width below the games of the call that is NOT the
+ * order of a sequential call (a game admitted late retires late); with width >= the games of the call it is diee_self_play_multi's order
+ * and output exactly.  stats[b].move_steps = 1 + the call's last move-step in which batch b had a live game; max_steps counts the call's
+ * move-steps.  outs / stats: [n_batches] as in diee_self_play_multi. */
+diee_status diee_self_play_refill(diee_ctx*, const diee_batch* batches, uint32_t n_batches, uint32_t width,
+                                  const diee_mcts_cfg* cfg, float temperature, uint32_t flags, uint32_t max_steps,
+                                  diee_fragments* outs, diee_stats* stats);
 
 /* ---- training-step kernels (no ctx: plain device pointers of the caller's framework, launched on `stream`, a
  * hipStream_t; NULL = the default stream).  AlphaZero::train (alphazero.rs:202-261) is tch autograd in the reference;

@@ -120,6 +120,23 @@ public:
         return out;
     }
 
+    // the same games with slot refill (opt-in, diee_self_play_refill: not the reference's loop): at most `width` in flight, a retired game's
+    // slot taken by the next unstarted game; always without the quirks.  Per call the same records as self_play_parallel(..., ref_quirks =
+    // false) up to their order (include/diee.h).
+    std::vector<std::vector<MemoryFragment>> self_play_refill(uint32_t self_play_iterations, uint32_t num_self_play_batches, uint32_t width,
+                                                              const MctsConfig& cfg, float temperature, uint64_t seed,
+                                                              std::vector<diee_stats>* stats = nullptr) {
+        std::vector<diee_batch> bt(self_play_iterations);
+        for (uint32_t i = 0; i < self_play_iterations; ++i) bt[i] = diee_batch{num_self_play_batches, 0u, seed + i};
+        std::vector<diee_fragments> fr(self_play_iterations);
+        std::vector<diee_stats> st(self_play_iterations);
+        chk(diee_self_play_refill(ctx_, bt.data(), self_play_iterations, width, &cfg, temperature, 0u, 0, fr.data(), st.data()));
+        std::vector<std::vector<MemoryFragment>> out;
+        for (auto& f : fr) out.push_back(take(f));
+        if (stats) *stats = st;
+        return out;
+    }
+
     diee_ctx* raw() { return ctx_; }
 
 private:
