@@ -15,6 +15,7 @@
 #include "nn_device.h"
 #include "launch.h"
 #include "mcts_device.h"
+#include "search_iter_device.h"
 #include "search_types.h"
 #include "wave_ops.h"
 
@@ -58,31 +59,6 @@ __global__ void k_init_roots(Tree T, Slots S, uint32_t n) {
 }
 
 // ---- selection ---------------------------------------------------------------------------------
-struct Best { float s; int j; };
-__device__ __forceinline__ Best better(Best a, Best b) {      // later index wins ties (Iterator::max_by)
-    if (b.j < 0) return a;
-    if (a.j < 0) return b;
-    if (a.s > b.s || (a.s == b.s && a.j > b.j)) return a;
-    return b;
-}
-
-// the best of the wave in every lane; `better` is a symmetric total order, so the pairing order is free (wave_ops.h)
-__device__ __forceinline__ Best wave_best(Best b) {
-    Best o;
-    o.s = dpp_f32<kDppXor1>(b.s); o.j = dpp_i32<kDppXor1>(b.j); b = better(b, o);
-    o.s = dpp_f32<kDppXor2>(b.s); o.j = dpp_i32<kDppXor2>(b.j); b = better(b, o);
-    o.s = dpp_f32<kDppHalfMirror>(b.s); o.j = dpp_i32<kDppHalfMirror>(b.j); b = better(b, o);
-    o.s = dpp_f32<kDppMirror>(b.s); o.j = dpp_i32<kDppMirror>(b.j); b = better(b, o);
-    const int si = __builtin_bit_cast(int, b.s);
-    Best r[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        r[q].s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 16 * q));
-        r[q].j = __builtin_amdgcn_readlane(b.j, 16 * q);
-    }
-    return better(better(r[0], r[1]), better(r[2], r[3]));
-}
-
 // alpha_select_leaf_node / select_alpha (alpha_mcts.rs:14-33) with alpha_ucb (node.rs:98-112):
 //   q + (c * (sqrt(N_parent) / (n + 1))) * p, f32, in this association; NaN compares Equal.
 // One memory round trip per level: a level reads the statistics of all children AND their headers (meta, first child), so
@@ -144,11 +120,7 @@ __device__ __forceinline__ void select_slot(const Tree& T, const Slots& S, const
                 cm = T.meta[ci]; cf = T.first_child[ci];
                 cs = load_state(&T.state[ci]);              // rides the same round trip: the leaf's state needs none of its own
             }
-            const float q = vis == 0.0f ? 0.0f : val / vis;
-            const float t = sq / (vis + 1.0f);
-            const float u = c * t;
-            const float w = u * pr;
-            const float s = q + w;
+            const float s = puct_score(vis, val, pr, sq, c);
             if (s != s) lastnan = (int)j;
             else if (b.j < 0 || !(b.s > s)) { b.s = s; b.j = (int)j; bm = cm; bf = cf; bv = vis; bs = cs; }
         }
@@ -161,11 +133,7 @@ __device__ __forceinline__ void select_slot(const Tree& T, const Slots& S, const
                 const size_t ci = base + fc + j;
                 const float vis = T.visits[ci], val = T.value[ci], pr = T.prior[ci];
                 const uint32_t cm = T.meta[ci], cf = T.first_child[ci];
-                const float q = vis == 0.0f ? 0.0f : val / vis;
-                const float t = sq / (vis + 1.0f);
-                const float u = c * t;
-                const float w = u * pr;
-                const float s = q + w;
+                const float s = puct_score(vis, val, pr, sq, c);
                 if (b.j < 0 || !(b.s > s)) { b.s = s; b.j = (int)j; bm = cm; bf = cf; bv = vis; }
             }
         }
@@ -214,18 +182,6 @@ __device__ __forceinline__ void select_slot(const Tree& T, const Slots& S, const
     }
 }
 
-// the slot's counters to and from registers (SC_ILLEGAL is only ever bumped by atomics in memory: it is not written back)
-__device__ __forceinline__ void load_counters(const Slots& S, uint32_t slot, uint32_t (&cn)[SC_COUNT]) {
-    static_assert(SC_COUNT == 8, "two 16-byte loads");
-    const uint4 a = ((const uint4*)(S.slot_cnt + slot * SC_COUNT))[0], b = ((const uint4*)(S.slot_cnt + slot * SC_COUNT))[1];
-    cn[0] = a.x; cn[1] = a.y; cn[2] = a.z; cn[3] = a.w; cn[4] = b.x; cn[5] = b.y; cn[6] = b.z; cn[7] = b.w;
-}
-__device__ __forceinline__ void store_counters(const Slots& S, uint32_t slot, const uint32_t (&cn)[SC_COUNT]) {
-    uint32_t* p = S.slot_cnt + slot * SC_COUNT;
-    ((uint4*)p)[0] = make_uint4(cn[0], cn[1], cn[2], cn[3]);
-    static_assert(SC_ILLEGAL == 6 && SC_NN_ROWS == 7, "word 6 stays in memory");
-    p[4] = cn[4]; p[5] = cn[5]; p[7] = cn[7];
-}
 // ---- expansion + backpropagation ---------------------------------------------------------------
 // dev builds (-DDIEE_EXPAND_STAMPS): shader-clock sums per phase of k_expand over all waves, read by scripts/expand_phases.py
 #ifdef DIEE_EXPAND_STAMPS
@@ -273,11 +229,9 @@ struct TwoScratch {
 // TWO == 2 (with PRE, the children exist already): wave 1 is the COMMIT wave -- softmax over the logits row, masked priors of the children --
 // while wave 0 evaluates the value head, backpropagates and descends; same meeting point, wave 1 hands the leaf's new header over in LDS and
 // wave 0 stores it (the descent may be reading that header: nobody else may change it under its feet).
-// The body of one (slot, iteration) of k_expand.  (k_tail, the tail of a batch, below, runs the same operations in the same order on an
-// LDS copy of the tree: what one changes in the arithmetic the other must follow -- tests/test_tail_gpu.py holds both to the oracle.)
-// k_tail requests its network row -- 22 logits per lane, the value features -- BEFORE it meets the other games: the round trip to where
-// the tower launch left them passes while the wave would wait anyway
-struct NetRowLoaded { ValueHeadIn vh; float lg[22]; };
+// The body of one (slot, iteration) of k_expand.  (k_tail and k_free, below, run the same operations in the same order on an LDS copy of
+// the tree; their one copy is search_iteration / select_level / end_selection in search_iter_device.h, and the score both sides compute is
+// that header's puct_score: a change of the arithmetic here has to be made there too -- the bit-exact suites hold both to the oracle.)
 template <bool PRE, int TWO>
 using ExpandScratchOf = typename std::conditional<(TWO != 0), TwoScratch, typename std::conditional<PRE, SettleScratch, ExpandScratch>::type>::type;
 template <bool PRE, int TWO = 0>
@@ -667,7 +621,8 @@ struct TailArgs { Tail L; uint32_t q; };
 // nodes) in LDS -- loaded when a launch starts, every update also written through to HBM (nodes past the capacity are read and
 // written there) --, and the selection record, the path of the last selection, the counters and the arena's fill mark in registers
 // from one iteration to the next.  A descent is LDS reads; the leaf's 32-byte state and its ring row are requested BEFORE the games
-// meet.  The arithmetic is select_slot's / expand_body's, operation for operation, in the same order per node.
+// meet.  The arithmetic is select_slot's / expand_body's, operation for operation, in the same order per node: the iteration itself is
+// search_iter_device.h's, shared with k_free; what is k_tail's own is the meetings, the take-in and the plan.
 struct TailTree {
     float vis[kTailLdsNodes], val[kTailLdsNodes], pri[kTailLdsNodes], cval[kTailLdsNodes];
     uint32_t meta[kTailLdsNodes], fc[kTailLdsNodes], crow[kTailLdsNodes];
@@ -683,21 +638,16 @@ struct TailLds {
 };
 static_assert(sizeof(TailLds) <= 160 * 1024, "one workgroup per CU");
 
-// the tree through LDS: nodes below kTailLdsNodes live there (and in HBM, written through), the others in HBM alone
-struct TreeLds {
-    const Tree& T; size_t base; TailTree& t;
-    __device__ __forceinline__ float vis(uint32_t i) const { return i < kTailLdsNodes ? t.vis[i] : T.visits[base + i]; }
-    __device__ __forceinline__ float val(uint32_t i) const { return i < kTailLdsNodes ? t.val[i] : T.value[base + i]; }
-    __device__ __forceinline__ float pri(uint32_t i) const { return i < kTailLdsNodes ? t.pri[i] : T.prior[base + i]; }
-    __device__ __forceinline__ uint32_t meta(uint32_t i) const { return i < kTailLdsNodes ? t.meta[i] : T.meta[base + i]; }
-    __device__ __forceinline__ uint32_t fc(uint32_t i) const { return i < kTailLdsNodes ? t.fc[i] : T.first_child[base + i]; }
-    __device__ __forceinline__ void add(uint32_t i, float v) const {          // visits += 1, value += v (simple_mcts.rs:96-103, one node)
-        const float nv = vis(i) + 1.0f, nw = val(i) + v;
-        if (i < kTailLdsNodes) { t.vis[i] = nv; t.val[i] = nw; }
-        T.visits[base + i] = nv; T.value[base + i] = nw;
-    }
+// the tree through LDS (StagedStats, cap = kTailLdsNodes) with Tree::meta and Tree::first_child as they are: 36 bytes per node
+struct TreeLds : StagedStats {
+    TailTree& t;
+    struct Hdr { uint32_t meta, first_child; __device__ __forceinline__ uint32_t bits() const { return meta; } };
+    __device__ __forceinline__ Hdr hdr(uint32_t i) const { return i < cap ? Hdr{t.meta[i], t.fc[i]} : Hdr{T.meta[base + i], T.first_child[base + i]}; }
+    __device__ __forceinline__ static uint32_t nch(const Hdr& h) { return meta_nch(h.meta); }
+    __device__ __forceinline__ static uint32_t fc(const Hdr& h) { return h.first_child; }
+    __device__ __forceinline__ uint32_t leaf_meta(uint32_t, const Hdr& h) const { return h.meta; }
     __device__ __forceinline__ void set_header(uint32_t i, uint32_t m, uint32_t f) const {
-        if (i < kTailLdsNodes) { t.meta[i] = m; t.fc[i] = f; }
+        if (i < cap) { t.meta[i] = m; t.fc[i] = f; }
         T.meta[base + i] = m; T.first_child[base + i] = f;
     }
 };
@@ -719,34 +669,19 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
     const size_t base = (size_t)slot * T.node_cap;
     uint32_t* crow_g = L.crow + (size_t)slot * T.node_cap;
     float* cval_g = L.cval + (size_t)slot * T.node_cap;
-    const TreeLds X{T, base, D.t};
+    const TreeLds X{{T, base, kTailLdsNodes, D.t.vis, D.t.val, D.t.pri}, D.t};
     const bool quirks = P.quirks != 0;
-    // ---- what the slot carries from launch to launch (the record select_slot / k_tail leave in HBM), into registers ----
-    const uint32_t seg = G.n == 1 ? 0u : S.seg[slot];
-    const uint32_t seg_first = G.first_slot[seg], seg_end = G.end_slot[seg];
-    const unsigned long long seed = G.seed[seg];
-    const uint32_t gid = S.game_id[slot], rnd = S.round[slot];
-    const float rv0 = S.root_value0[seg];
-    unsigned long long evals = S.counters[(size_t)seg * CNT_COUNT + CNT_NN_EVALS];
-    uint32_t used = T.used[slot];
-    bool lterm = S.leaf_term[slot] != 0;
-    uint32_t leaf = S.leaf[slot], sel = S.sel[slot], leaf_meta = S.leaf_meta[slot];
-    float sel_value = S.sel_value[slot];
-    uint32_t plen = S.path_len[slot];
-    uint32_t pnode = S.path[(size_t)slot * kPathCap + lane];     // lane d: the node at depth d of the last real selection's path
-    uint32_t cn[SC_COUNT];
-    load_counters(S, slot, cn);
-    const BgState rs = load_state(&T.state[base]);
-    const int root_player = st_player(rs);
+    SlotRecord R;                                               // what the slot carries from launch to launch, into registers
+    R.load(T, S, G, slot, lane);
     // every game of the batch held a real selection when the previous launch ended (it never loses it): no slot can still be counted
     // as a stale INITIAL one (Q14), so the batch's first slot need not look at an iteration's flag words for that
     bool all_sel = false;
-    if (quirks && slot == seg_first) {
-        const uint32_t g = seg_first + (uint32_t)lane;
-        all_sel = __ballot(g < seg_end && S.sel[g] == kNone) == 0ull && seg_end - seg_first <= 64u;
+    if (quirks && slot == R.seg_first) {
+        const uint32_t g = R.seg_first + (uint32_t)lane;
+        all_sel = __ballot(g < R.seg_end && S.sel[g] == kNone) == 0ull && R.seg_end - R.seg_first <= 64u;
     }
     // ---- the tree's statistics into LDS; the rows of tower launch q - 1 on top ----
-    const uint32_t nl = used < kTailLdsNodes ? used : kTailLdsNodes;
+    const uint32_t nl = R.used < kTailLdsNodes ? R.used : kTailLdsNodes;
     for (uint32_t i = lane; i < nl; i += 64) {
         D.t.vis[i] = T.visits[base + i]; D.t.val[i] = T.value[base + i]; D.t.pri[i] = T.prior[base + i];
         D.t.meta[i] = T.meta[base + i]; D.t.fc[i] = T.first_child[base + i];
@@ -755,21 +690,18 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
     __syncthreads();
     // children the plan of launch q - 1 created ahead for this game's demanded leaf (child_rows) sit at [used, ahead_hi): evaluated before their
     // parent is expanded -- which the first iteration below does, creating exactly these nodes; it must not clear their rows then
-    uint32_t ahead_hi = used;
+    uint32_t ahead_hi = R.used;
     if (A.q > 0) {
         if (L.child_rows > 0) {
-            for (uint32_t i = used + (uint32_t)lane; i < used + (uint32_t)kMaxPlays && i < kTailLdsNodes; i += 64) { D.t.crow[i] = 0; D.t.cval[i] = 0.0f; }
+            for (uint32_t i = R.used + (uint32_t)lane; i < R.used + (uint32_t)kMaxPlays && i < kTailLdsNodes; i += 64) { D.t.crow[i] = 0; D.t.cval[i] = 0.0f; }
             __syncthreads();
         }
         const uint32_t pq = A.q - 1, nr = L.n_rows[pq] < L.rows ? L.n_rows[pq] : L.rows;
         for (uint32_t r = lane; r < nr; r += 64) {
             const uint32_t rn = L.rows_node[pq * L.rows + r];
             if ((rn >> 24) == slot) {
-                const float* h = L.hv + (size_t)(pq * L.rows + r) * 72;
-                float dot = 0.0f;
-                for (int i = 0; i < 72; ++i) dot += h[i] * S.wv[i];
                 const uint32_t node = rn & 0xFFFFFFu;
-                const float cv = tanhf(dot + S.wv[72]);
+                const float cv = row_value(L.hv + (size_t)(pq * L.rows + r) * 72, S.wv);
                 cval_g[node] = cv; crow_g[node] = pq * L.rows + r + 1u;
                 if (node < kTailLdsNodes) { D.t.cval[node] = cv; D.t.crow[node] = pq * L.rows + r + 1u; }
                 if (node >= ahead_hi) ahead_hi = node + 1u;
@@ -779,13 +711,14 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
         __syncthreads();
     }
     TL_STAMP(0);
-    BgState lst = load_state(&S.eval_states[slot]);             // the selected leaf's state
+    R.lst = load_state(&S.eval_states[slot]);                   // the selected leaf's state
+    const IterScratch scratch{&D.ws, D.lgs, D.raw, D.code};
     bool hit = false;
     uint32_t misses = 0;
     for (;;) {
-        const uint32_t cr = lterm ? 0u : (leaf < kTailLdsNodes ? D.t.crow[leaf] : crow_g[leaf]);
-        hit = lterm || cr != 0u;
-        const uint32_t ring = (lterm || cr == 0u) ? 0u : cr - 1u;
+        const uint32_t cr = R.lterm ? 0u : (R.leaf < kTailLdsNodes ? D.t.crow[R.leaf] : crow_g[R.leaf]);
+        hit = R.lterm || cr != 0u;
+        const uint32_t ring = (R.lterm || cr == 0u) ? 0u : cr - 1u;
         NetRowLoaded pre;                                       // requested now, used behind the meeting
         pre.vh = value_head_load(L.hv + (size_t)ring * 72, S.wv, lane);
         softmax_load(L.logits + (size_t)ring * 1352, lane, pre.lg);
@@ -795,150 +728,35 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
         }
         TL_STAMP(1);
         if (misses != 0u) break;
-        // ================= iteration `it` (expand_body<false, 0>'s operations, in its order) =================
-        uint32_t* iflag = S.iter_flags + 2 * ((size_t)seg * G.iter_cap + it);
+        // ================= iteration `it` (search_iter_device.h) =================
         // the flag words matter to a game whose leaf is a finished game (`continue`, stale slot) and to the batch's first slot
         uint2 ifl = make_uint2(1u, 0u);
-        if (lterm || (quirks && slot == seg_first && !all_sel)) ifl = *(const uint2*)iflag;
-        const bool active = ifl.x != 0u;
-        float v = 0.0f;
-        bool do_expand = !lterm, do_backprop = true;
-        if (active) {
-            if (slot == seg_first) evals += (unsigned long long)(seg_end - seg_first);
-            if (lterm) {
-                do_expand = false; do_backprop = false;
-                if (quirks && sel != kNone) {                   // the stale slot is backpropagated with its own value again (Q14)
-                    if (plen) { if ((uint32_t)lane < plen) X.add(pnode, sel_value); }
-                    else if (lane == 0) { for (uint32_t i = sel; i != kNone; i = T.parent[base + i]) X.add(i, sel_value); }
-                }
-            } else {
-                v = value_head_eval(pre.vh, lane);
-                sel_value = v;
+        if (R.lterm || (quirks && slot == R.seg_first && !all_sel)) ifl = *(const uint2*)(S.iter_flags + 2 * ((size_t)R.seg * G.iter_cap + it));
+        search_iteration(S, R, X, pre, scratch, ifl, it, slot, lane, quirks, [&](uint32_t cl, float prj, uint32_t cm) {
+            if (cl < kTailLdsNodes) {
+                D.t.vis[cl] = 0.0f; D.t.val[cl] = 0.0f; D.t.pri[cl] = prj; D.t.meta[cl] = cm; D.t.fc[cl] = 0;
+                if (cl >= ahead_hi) { D.t.crow[cl] = 0; D.t.cval[cl] = 0.0f; }       // (below: evaluated ahead, or cleared at the take-in)
             }
-            const uint32_t m0 = lterm ? 0u : leaf_meta;
-            if (do_expand && !(m0 & kDrained)) {
-                int k = bg_legal_plays_wave(lst, &D.ws, lane, S.overflow);
-                if (k > kMaxPlays) { if (lane == 0) atomicOr(S.overflow, 1u); k = 0; }
-                const int r0 = st_roll(lst, 0), r1 = st_roll(lst, 1);
-                float smM, smInv;
-                softmax_reduce(pre.lg, lane, smM, smInv);
-#pragma unroll
-                for (int q = 0; q < 22; ++q) D.lgs[lane + 64 * q] = pre.lg[q];
-                __syncthreads();
-                for (int j = lane; j < k; j += 64) {
-                    const uint32_t code = bg_encode_dev(r0, r1, D.ws.play[j]);
-                    D.raw[j] = softmax_prob(D.lgs[code], smM, smInv); D.code[j] = (uint16_t)code;
-                }
-                __syncthreads();
-                float pr[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pr[r] = lane + 64 * r < k ? D.raw[lane + 64 * r] : 0.0f;
-                float sum = 0.0f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int kr = k - 64 * r < 64 ? k - 64 * r : 64;                    // uniform
-                    for (int j = 0; j < kr; ++j) sum += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pr[r]), j));
-                }
-                const uint32_t first = used;
-                if (first + (uint32_t)k > T.node_cap) {
-                    if (lane == 0) atomicOr(S.overflow, 2u);
-                } else {
-                    const uint32_t e = it + 1u;
-                    for (int j = lane; j < k; j += 64) {
-                        const uint32_t cl = first + (uint32_t)j;
-                        const size_t ci = base + cl;
-                        BgState cs = lst;
-                        int d0, d1;
-                        draw_dice(seed, gid, rnd, e, (uint32_t)j, d0, d1);      // child dice frozen at creation (Q9)
-                        bg_apply_dev(cs, D.ws.play[j], d0, d1);
-                        store_state(&T.state[ci], cs);
-                        const float prj = D.raw[j] / sum;
-                        const uint32_t cm = (uint32_t)D.code[j] | meta_terminal_bits(cs);
-                        T.visits[ci] = 0.0f; T.value[ci] = 0.0f; T.prior[ci] = prj;
-                        T.parent[ci] = leaf; T.first_child[ci] = 0; T.meta[ci] = cm;
-                        if (cl < kTailLdsNodes) {
-                            D.t.vis[cl] = 0.0f; D.t.val[cl] = 0.0f; D.t.pri[cl] = prj; D.t.meta[cl] = cm; D.t.fc[cl] = 0;
-                            if (cl >= ahead_hi) { D.t.crow[cl] = 0; D.t.cval[cl] = 0.0f; }       // (below: evaluated ahead, or cleared at the take-in)
-                        }
-                    }
-                    const uint32_t nmeta = kDrained | ((uint32_t)k << 16) | (m0 & kMetaKeep);
-                    if (lane == 0) X.set_header(leaf, nmeta, first);
-                    used = first + (uint32_t)k;
-                    cn[SC_EXPANSIONS] += 1; cn[SC_CHILDREN] += (uint32_t)k;
-                    if ((uint32_t)k > cn[SC_MAX_CHILDREN]) cn[SC_MAX_CHILDREN] = (uint32_t)k;
-                }
-                __syncthreads();
-            }
-            if (do_backprop) {
-                if (plen) { if ((uint32_t)lane < plen) X.add(pnode, v); }
-                else if (lane == 0) { for (uint32_t i = leaf; i != kNone; i = T.parent[base + i]) X.add(i, v); }
-            }
-            if (quirks && slot == seg_first && ifl.y != 0u && lane == 0) {
-                // slots still holding the initial 0 index re-backpropagate node 0 = this root with the NN value of its state (Q14)
-                float rvis = X.vis(0), rval = X.val(0);
-                for (uint32_t i = 0; i < ifl.y; ++i) { rvis += 1.0f; rval += rv0; }
-                D.t.vis[0] = rvis; D.t.val[0] = rval; T.visits[base] = rvis; T.value[base] = rval;
-            }
-            __syncthreads();
-        }
+        });
         // ================= selection for iteration it + 1 (select_slot on the LDS copy) =================
         if (it + 1 < L.iterations) {
-            uint32_t* nflag = S.iter_flags + 2 * ((size_t)seg * G.iter_cap + it + 1);
+            uint32_t* nflag = S.iter_flags + 2 * ((size_t)R.seg * G.iter_cap + it + 1);
             uint32_t node = 0, depth = 0, mine = lane == 0 ? 0u : kNone;
-            uint32_t mt = X.meta(0), fcn = X.fc(0);
+            TreeLds::Hdr h = X.hdr(0);
             float nvis = X.vis(0);
             for (;;) {
-                const uint32_t k = meta_nch(mt);
+                const uint32_t k = X.nch(h);
                 if (k == 0) break;
-                const float sq = sqrtf(nvis);
-                Best b{0.0f, -1};
-                int lastnan = -1;
-                for (uint32_t j = lane; j < k; j += 64) {
-                    const uint32_t ci = fcn + j;
-                    const float vis = X.vis(ci), val = X.val(ci), pr = X.pri(ci);
-                    const float q = vis == 0.0f ? 0.0f : val / vis;
-                    const float t = sq / (vis + 1.0f);
-                    const float u = c * t;
-                    const float w = u * pr;
-                    const float sc_ = q + w;
-                    if (sc_ != sc_) lastnan = (int)j;
-                    else if (b.j < 0 || !(b.s > sc_)) { b.s = sc_; b.j = (int)j; }
-                }
-                lastnan = wave_allmax_i32(lastnan);
-                if (lastnan >= 0) {                             // the sequential fold restarts after a NaN: only children after the last NaN compete
-                    b.s = 0.0f; b.j = -1;
-                    for (uint32_t j = lane; j < k; j += 64) {
-                        if ((int)j <= lastnan) continue;
-                        const uint32_t ci = fcn + j;
-                        const float vis = X.vis(ci), val = X.val(ci), pr = X.pri(ci);
-                        const float q = vis == 0.0f ? 0.0f : val / vis;
-                        const float t = sq / (vis + 1.0f);
-                        const float u = c * t;
-                        const float w = u * pr;
-                        const float sc_ = q + w;
-                        if (b.j < 0 || !(b.s > sc_)) { b.s = sc_; b.j = (int)j; }
-                    }
-                }
-                b = wave_best(b);
-                const int chosen = b.j >= 0 ? b.j : lastnan;
-                node = fcn + (uint32_t)chosen;
+                node = X.fc(h) + select_level(X, X.fc(h), k, sqrtf(nvis), c, lane);
                 ++depth;
                 if ((uint32_t)lane == depth) mine = node;
-                mt = X.meta(node); fcn = X.fc(node); nvis = X.vis(node);
+                h = X.hdr(node); nvis = X.vis(node);
             }
-            const uint32_t npl = depth < S.path_cap ? depth + 1u : 0u;
-            cn[SC_SELECTIONS] += 1; cn[SC_DEPTH_SUM] += depth;
-            if (mt & kMetaTerminal) {                           // a finished game: +-1 for the ROOT's player (alpha_mcts.rs:157-163)
-                const float tv = ((mt & kMetaWinnerPlus) ? 1 : -1) == root_player ? 1.0f : -1.0f;
-                if (npl) { if ((uint32_t)lane < npl) X.add(mine, tv); }
-                else if (lane == 0) { for (uint32_t i = node; i != kNone; i = T.parent[base + i]) X.add(i, tv); }
-                cn[SC_TERMINAL] += 1;
-                lterm = true;
-                if (lane == 0 && quirks && sel == kNone) atomicAdd(&nflag[1], 1u);
+            if (end_selection(S, R, X, node, depth, mine, h, lane)) {
+                if (lane == 0 && quirks && R.sel == kNone) atomicAdd(&nflag[1], 1u);
             } else {
-                lterm = false; leaf = node; sel = node; leaf_meta = mt; plen = npl; pnode = mine;
+                R.sel = node;
                 if (lane == 0) nflag[0] = 1u;
-                lst = load_state(&T.state[base + node]);        // in flight while the games meet
             }
         }
         ++it;
@@ -946,15 +764,7 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
         TL_STAMP(2); TL_COUNT(6);
         if (it >= L.iterations) break;
     }
-    // ---- the record for the next launch (and for whoever reads the slot after the search) ----
-    if (lane == 0) {
-        S.leaf_term[slot] = lterm ? 1 : 0; S.leaf[slot] = leaf; S.sel[slot] = sel; S.leaf_meta[slot] = leaf_meta;
-        S.sel_value[slot] = sel_value; S.path_len[slot] = (uint8_t)plen;
-        T.used[slot] = used;
-        if (slot == seg_first) S.counters[(size_t)seg * CNT_COUNT + CNT_NN_EVALS] = evals;
-        store_state(&S.eval_states[slot], lst);
-    }
-    if ((uint32_t)lane < plen) S.path[(size_t)slot * kPathCap + lane] = pnode;
+    R.store(T, S, slot, lane);
     const bool done = it >= L.iterations;
     uint32_t mine_rows = 0, ncand = 0;
     if (!done) {
@@ -966,7 +776,7 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
         // Heuristic only: which rows a launch carries beside the demanded ones never shows in a result. ----
         const uint32_t room = L.rows - (misses < L.rows ? misses : L.rows);
         const uint32_t want0 = room / n + (slot < room % n ? 1u : 0u), want = want0 < 63u ? want0 : 63u;
-        const uint32_t nu = used < kTailLdsNodes ? used : kTailLdsNodes;
+        const uint32_t nu = R.used < kTailLdsNodes ? R.used : kTailLdsNodes;
         // extra_rows: where the rows of a launch are scarce (fewer than 8 per game) a game looks for a few candidates beyond its share; they take
         // the rows that games with nothing worth evaluating (finished-game leaves, narrow bear-off trees) leave free -- after every game has taken
         // its share (one more meeting; the conditions are the same in every workgroup)
@@ -976,38 +786,18 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
         if (want_x > 0 && L.rollout_steps > 0) {
             for (uint32_t i = lane; i < nu; i += 64) { D.vvis[i] = D.t.vis[i]; D.vval[i] = D.t.val[i]; }
             __syncthreads();
-            const uint32_t demanded = hit ? kNone : leaf;
+            const uint32_t demanded = hit ? kNone : R.leaf;
             uint32_t fruitless = 0;
             for (uint32_t step = 0; step < L.rollout_steps && ncand < want_x && fruitless < 8; ++step) {
-                uint32_t node = 0, depth = 0, mine = lane == 0 ? 0u : kNone, mt = 0;
-                for (;;) {
-                    mt = X.meta(node);
-                    const uint32_t k = meta_nch(mt);
-                    if (k == 0) break;
-                    const uint32_t fcn = X.fc(node);
-                    const float sq = sqrtf(node < nu ? D.vvis[node] : T.visits[base + node]);
-                    Best b{0.0f, -1};
-                    for (uint32_t j = lane; j < k; j += 64) {
-                        const uint32_t ci = fcn + j;
-                        const float vis = ci < nu ? D.vvis[ci] : T.visits[base + ci], val = ci < nu ? D.vval[ci] : T.value[base + ci];
-                        const float q = vis == 0.0f ? 0.0f : val / vis;
-                        const float sc_ = q + (c * (sq / (vis + 1.0f))) * X.pri(ci);
-                        if (sc_ == sc_ && (b.j < 0 || !(b.s > sc_))) { b.s = sc_; b.j = (int)j; }
-                    }
-                    b = wave_best(b);
-                    node = fcn + (uint32_t)(b.j >= 0 ? b.j : (int)k - 1);
-                    ++depth;
-                    if ((uint32_t)lane == depth) mine = node;
-                    if (depth >= 63) break;
-                }
-                const uint32_t cr = node < kTailLdsNodes ? D.t.crow[node] : crow_g[node];
+                const VirtualDescent d = virtual_descent<true>(X, D.vvis, D.vval, nu, c, lane);
+                const uint32_t node = d.node, cr = node < kTailLdsNodes ? D.t.crow[node] : crow_g[node];
                 float x = 0.0f;
                 bool fresh = false;
-                if (mt & kMetaTerminal) x = ((mt & kMetaWinnerPlus) ? 1 : -1) == root_player ? 1.0f : -1.0f;
+                if (d.bits & kMetaTerminal) x = finished_value(d.bits, R.root_player);
                 else if (cr != 0) x = node < kTailLdsNodes ? D.t.cval[node] : cval_g[node];
-                else if (!(mt & kDrained) && node != demanded) fresh = __ballot((uint32_t)lane < ncand && D.cand[lane] == node) == 0ull;
+                else if (!(d.bits & kDrained) && node != demanded) fresh = __ballot((uint32_t)lane < ncand && D.cand[lane] == node) == 0ull;
                 if (fresh) { if (lane == 0) D.cand[ncand] = node; ++ncand; fruitless = 0; } else ++fruitless;
-                if ((uint32_t)lane <= depth && mine < nu) { D.vvis[mine] += 1.0f; D.vval[mine] += x; }
+                virtual_visit(d, D.vvis, D.vval, nu, x, lane);
                 __syncthreads();
             }
         }
@@ -1016,9 +806,9 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
         // deepens (select the node just expanded's best child, expand it, select ITS best child ...) otherwise misses at every iteration.  Up to
         // child_rows of them, in play order (the priors that rank them are in the evaluation the leaf is waiting for), from the rows the shares leave free.
         uint32_t nchild = 0;
-        if (L.child_rows > 0 && !hit && !(leaf_meta & kDrained)) {
-            int k = bg_legal_plays_wave(lst, &D.ws, lane, S.overflow);
-            if (k > kMaxPlays || used + (uint32_t)k > T.node_cap) k = 0;                              // (the expansion itself will report it)
+        if (L.child_rows > 0 && !hit && !(R.leaf_meta & kDrained)) {
+            int k = bg_legal_plays_wave(R.lst, &D.ws, lane, S.overflow);
+            if (k > kMaxPlays || R.used + (uint32_t)k > T.node_cap) k = 0;                              // (the expansion itself will report it)
             nchild = (uint32_t)k < L.child_rows ? (uint32_t)k : L.child_rows;
             __syncthreads();
         }
@@ -1028,9 +818,9 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
         if (lane == 0 && mine_rows) start = atomicAdd(&L.n_rows[A.q], mine_rows);
         start = (uint32_t)__builtin_amdgcn_readfirstlane((int)start);
         if ((uint32_t)lane < mine_rows && start + (uint32_t)lane < L.rows) {
-            const uint32_t node = (dem && lane == 0) ? leaf : D.cand[(uint32_t)lane - dem];
+            const uint32_t node = (dem && lane == 0) ? R.leaf : D.cand[(uint32_t)lane - dem];
             const uint32_t r = A.q * L.rows + start + (uint32_t)lane;
-            store_state(&L.rows_state[r], (dem && lane == 0) ? lst : load_state(&T.state[base + node]));
+            store_state(&L.rows_state[r], (dem && lane == 0) ? R.lst : load_state(&T.state[base + node]));
             L.rows_node[r] = (slot << 24) | node;
         }
         uint32_t extra = 0;
@@ -1050,12 +840,12 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
             for (uint32_t j = (uint32_t)lane; j < extra; j += 64) {
                 const uint32_t r = A.q * L.rows + start2 + j;
                 if (j < nchild) {                                                               // the demanded leaf's children, as iteration `it` will create them
-                    BgState cs = lst;
+                    BgState cs = R.lst;
                     int d0, d1;
-                    draw_dice(seed, gid, rnd, it + 1u, j, d0, d1);
+                    draw_dice(R.seed, R.gid, R.rnd, it + 1u, j, d0, d1);
                     bg_apply_dev(cs, D.ws.play[j], d0, d1);
                     store_state(&L.rows_state[r], cs);
-                    L.rows_node[r] = (slot << 24) | (used + j);
+                    L.rows_node[r] = (slot << 24) | (R.used + j);
                 } else {
                     const uint32_t node = D.cand[share + (j - nchild)];
                     store_state(&L.rows_state[r], load_state(&T.state[base + node]));
@@ -1063,10 +853,10 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
                 }
             }
         }
-        cn[SC_NN_ROWS] += mine_rows + extra;
+        R.cn[SC_NN_ROWS] += mine_rows + extra;
         if (lane == 0 && share + extra) atomicAdd(&L.state[3], share + extra);
     }
-    if (lane == 0) store_counters(S, slot, cn);
+    if (lane == 0) store_counters(S, slot, R.cn);
     TL_STAMP(3);
     if (slot == 0 && lane == 0 && !done) L.n_dem[A.q] = misses;
     if (slot == 0 && lane == 0) {
@@ -1083,7 +873,7 @@ __global__ __launch_bounds__(64) void k_tail(Tree T, Slots S, Segs G, uint32_t n
 // ---- k_free: the free-running search (search_types.h, Free) -------------------------------------------------------------------------
 // One wave per live game, nobody waits for anybody.  Per launch a game (a) stages its tree's statistics in LDS (its share of the CU's
 // 160 KB: `lds_nodes` nodes, the rest is read in place) and takes in the rows the previous launch evaluated for it, (b) runs ITS OWN
-// iterations -- k_tail's body, i.e. expand_body's / select_slot's operations in their order -- for as long as its selected leaf is a
+// iterations -- search_iter_device.h's, the copy k_tail runs too: expand_body's / select_slot's operations in their order -- for as long as its selected leaf is a
 // finished game or has its evaluation in the ring and the flag words it needs are final, (c) lists its wishes for the next launch.
 // What couples the games of a batch (Q14): a game whose leaf is a finished game needs `node_selected` of its iteration, which is final
 // once it reads 1 or once every game of the batch has published that iteration's selection; the batch's first slot needs the count of
@@ -1125,21 +915,17 @@ __host__ __device__ __forceinline__ constexpr uint32_t hdr_fc(uint32_t h) { retu
 __host__ __device__ constexpr size_t free_lds_bytes(uint32_t ln) {
     return (size_t)ln * kFreeLdsNodeBytes + sizeof(WaveScratch) + sizeof(float) * kMaxPlays + sizeof(uint16_t) * kMaxPlays + sizeof(uint32_t) * 64u;
 }
-// the tree through LDS with a run-time capacity: nodes below `ln` live there (and in HBM, written through), the others in HBM alone
-struct TreeF {
-    const Tree& T; size_t base; uint32_t ln;
-    float *lvis, *lval, *lpri; uint32_t* lhdr;
-    __device__ __forceinline__ float vis(uint32_t i) const { return i < ln ? lvis[i] : T.visits[base + i]; }
-    __device__ __forceinline__ float val(uint32_t i) const { return i < ln ? lval[i] : T.value[base + i]; }
-    __device__ __forceinline__ float pri(uint32_t i) const { return i < ln ? lpri[i] : T.prior[base + i]; }
-    __device__ __forceinline__ uint32_t hdr(uint32_t i) const { return i < ln ? lhdr[i] : free_hdr(T.meta[base + i], T.first_child[base + i]); }
-    __device__ __forceinline__ void add(uint32_t i, float v) const {          // visits += 1, value += v (simple_mcts.rs:96-103, one node)
-        const float nv = vis(i) + 1.0f, nw = val(i) + v;
-        if (i < ln) { lvis[i] = nv; lval[i] = nw; }
-        T.visits[base + i] = nv; T.value[base + i] = nw;
-    }
+// the tree through LDS with a run-time capacity (StagedStats, cap = lds_nodes) and the packed header word
+struct TreeF : StagedStats {
+    uint32_t* lhdr;
+    struct Hdr { uint32_t w; __device__ __forceinline__ uint32_t bits() const { return w; } };      // free_hdr's packed word
+    __device__ __forceinline__ Hdr hdr(uint32_t i) const { return Hdr{i < cap ? lhdr[i] : free_hdr(T.meta[base + i], T.first_child[base + i])}; }
+    __device__ __forceinline__ static uint32_t nch(const Hdr& h) { return hdr_nch(h.w); }
+    __device__ __forceinline__ static uint32_t fc(const Hdr& h) { return hdr_fc(h.w); }
+    // (the header word in LDS carries no action code: the expansion of a leaf keeps it, kMetaKeep)
+    __device__ __forceinline__ uint32_t leaf_meta(uint32_t i, const Hdr&) const { return T.meta[base + i]; }
     __device__ __forceinline__ void set_header(uint32_t i, uint32_t m, uint32_t f) const {
-        if (i < ln) lhdr[i] = free_hdr(m, f);
+        if (i < cap) lhdr[i] = free_hdr(m, f);
         T.meta[base + i] = m; T.first_child[base + i] = f;
     }
 };
@@ -1179,33 +965,18 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
     const size_t base = (size_t)slot * T.node_cap;
     uint32_t* crow_g = F.crow + base;
     float* cval_g = F.cval + base;
-    const TreeF X{T, base, ln, lvis, lval, lpri, lhdr};
+    const TreeF X{{T, base, ln, lvis, lval, lpri}, lhdr};
     const bool quirks = P.quirks != 0;
-    // ---- the record the game carries from launch to launch ----
-    const uint32_t seg = G.n == 1 ? 0u : S.seg[slot];
-    const uint32_t seg_first = G.first_slot[seg], seg_end = G.end_slot[seg];
-    const unsigned long long seed = G.seed[seg];
-    const uint32_t gid = S.game_id[slot], rnd = S.round[slot];
-    const float rv0 = S.root_value0[seg];
-    unsigned long long evals = S.counters[(size_t)seg * CNT_COUNT + CNT_NN_EVALS];
-    uint32_t used = T.used[slot];
-    bool lterm = S.leaf_term[slot] != 0;
-    uint32_t leaf = S.leaf[slot], sel = S.sel[slot], leaf_meta = S.leaf_meta[slot];
-    float sel_value = S.sel_value[slot];
-    uint32_t plen = S.path_len[slot];
-    uint32_t pnode = S.path[(size_t)slot * kPathCap + lane];
-    uint32_t cn[SC_COUNT];
-    load_counters(S, slot, cn);
-    const BgState rs = load_state(&T.state[base]);
-    const int root_player = st_player(rs);
+    SlotRecord R;                                               // the record the game carries from launch to launch
+    R.load(T, S, G, slot, lane);
     // Q14's count of stale INITIAL slots matters to the batch's first slot for iterations before every game of the batch has had a real
     // selection: `fsel` = the latest first selection in the batch as the previous launches left it (a conservative bound: later is safe)
     // (k_free_first_sel wrote every game's word before round 0: another game's record -- S.sel -- is rewritten by its own workgroup when it leaves
     // the launch, which may be before this one gets here)
     uint32_t fsel = 0;
-    if (quirks && slot == seg_first) {
+    if (quirks && slot == R.seg_first) {
         uint32_t m = 0;
-        for (uint32_t g = seg_first + (uint32_t)lane; g < seg_end; g += 64) {
+        for (uint32_t g = R.seg_first + (uint32_t)lane; g < R.seg_end; g += 64) {
             const uint32_t f = F.first_sel[g];
             m = f == kNone ? 0x7fffffffu : (f > m ? f : m);
             if (f == kNone) break;
@@ -1213,7 +984,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
         fsel = (uint32_t)wave_allmax_i32((int)m);
     }
     // ---- the tree's statistics into LDS; the rows the previous launch evaluated for this game on top ----
-    const uint32_t nl = used < ln ? used : ln;
+    const uint32_t nl = R.used < ln ? R.used : ln;
     for (uint32_t i0 = 0; i0 < nl; i0 += 256) {                 // four rounds of loads in flight before the first store (a wave alone on its SIMD waits out every round trip)
         float a[4], b[4], p[4], cv4[4]; uint32_t m[4], f[4], r[4];
 #pragma unroll
@@ -1235,15 +1006,12 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
         for (uint32_t r = lane; r < cnt; r += 64) {
             const uint32_t row = off + r;
             const uint32_t node = F.rows_idx[rb + row] - (uint32_t)base;
-            const float* h = F.hv + (rb + row) * 72;
-            float dot = 0.0f;
-            for (int i = 0; i < 72; ++i) dot += h[i] * S.wv[i];
-            const float cv = tanhf(dot + S.wv[72]);
+            const float cv = row_value(F.hv + (rb + row) * 72, S.wv);
             const uint32_t id = ((pq << kFreeRowBits) | row) + 1u;
             cval_g[node] = cv; crow_g[node] = id;
             if (node < ln) { lcrow[node] = id; lcval[node] = cv; }
         }
-        cn[SC_NN_ROWS] += cnt;
+        R.cn[SC_NN_ROWS] += cnt;
         __syncthreads();
     }
     // a ring row is there while no later launch has reused its place: launch lq's rows until launch lq + ring is evaluated
@@ -1252,10 +1020,11 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
     // the least progress of the batch's games, as published (own included)
     auto batch_progress = [&]() {
         int m = 0x7fffffff;
-        for (uint32_t g = seg_first + (uint32_t)lane; g < seg_end; g += 64) { const int v = (int)free_load(&F.prog[g]); m = v < m ? v : m; }
+        for (uint32_t g = R.seg_first + (uint32_t)lane; g < R.seg_end; g += 64) { const int v = (int)free_load(&F.prog[g]); m = v < m ? v : m; }
         return (uint32_t)(-wave_allmax_i32(-m));
     };
-    BgState lst = load_state(&S.eval_states[slot]);             // the selected leaf's state
+    R.lst = load_state(&S.eval_states[slot]);                   // the selected leaf's state
+    const IterScratch scratch{&ws, lgs, raw, code};
     FR_STAMP(0);
     bool have = false, stalled = false;
     uint32_t minprog = 0;                                       // a lower bound of the batch's progress (every game has published iteration 0's selection)
@@ -1268,18 +1037,18 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
         softmax_load(F.logits + ring * 1352, lane, p.lg);
         return p;
     };
-    uint32_t cr = lterm ? 0u : crow_of(leaf);
+    uint32_t cr = R.lterm ? 0u : crow_of(R.leaf);
     NetRowLoaded pre;
-    if (!lterm && at_hand(cr)) pre = net_row(cr);
+    if (!R.lterm && at_hand(cr)) pre = net_row(cr);
     uint32_t ran = 0;
     for (;; ++ran) {
-        have = lterm || at_hand(cr);
+        have = R.lterm || at_hand(cr);
         if (!have) break;
         if (ran >= iter_cap) { stalled = true; break; }       // (enough for this launch: the other games' workgroups are done long since)
         // ---- the flag words of this iteration, where the game needs them ----
-        uint32_t* iflag = S.iter_flags + 2 * ((size_t)seg * G.iter_cap + it);
-        const bool need_cnt = quirks && slot == seg_first && it < fsel;
-        const bool need_any = lterm && (quirks || slot == seg_first);
+        uint32_t* iflag = S.iter_flags + 2 * ((size_t)R.seg * G.iter_cap + it);
+        const bool need_cnt = quirks && slot == R.seg_first && it < fsel;
+        const bool need_any = R.lterm && (quirks || slot == R.seg_first);
         uint2 ifl = make_uint2(1u, 0u);
         if (need_any || need_cnt) {
             bool fin = false;
@@ -1298,97 +1067,21 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
             if (!fin) { stalled = true; break; }
         }
         FR_STAMP(1);
-        // ================= iteration `it` (expand_body<false, 0>'s operations, in its order) =================
-        const bool active = ifl.x != 0u;
-        float v = 0.0f;
-        bool do_expand = !lterm, do_backprop = true;
-        if (active) {
-            if (slot == seg_first) evals += (unsigned long long)(seg_end - seg_first);
-            if (lterm) {
-                do_expand = false; do_backprop = false;
-                if (quirks && sel != kNone) {                   // the stale slot is backpropagated with its own value again (Q14)
-                    if (plen) { if ((uint32_t)lane < plen) X.add(pnode, sel_value); }
-                    else if (lane == 0) { for (uint32_t i = sel; i != kNone; i = T.parent[base + i]) X.add(i, sel_value); }
-                }
-            } else {
-                v = value_head_eval(pre.vh, lane);
-                sel_value = v;
-            }
-            const uint32_t m0 = lterm ? 0u : leaf_meta;
-            if (do_expand && !(m0 & kDrained)) {
-                int k = bg_legal_plays_wave(lst, &ws, lane, S.overflow);
-                if (k > kMaxPlays) { if (lane == 0) atomicOr(S.overflow, 1u); k = 0; }
-                const int r0 = st_roll(lst, 0), r1 = st_roll(lst, 1);
-                float smM, smInv;
-                softmax_reduce(pre.lg, lane, smM, smInv);
-#pragma unroll
-                for (int q = 0; q < 22; ++q) lgs[lane + 64 * q] = pre.lg[q];
-                __syncthreads();
-                for (int j = lane; j < k; j += 64) {
-                    const uint32_t cd = bg_encode_dev(r0, r1, ws.play[j]);
-                    raw[j] = softmax_prob(lgs[cd], smM, smInv); code[j] = (uint16_t)cd;
-                }
-                __syncthreads();
-                float pr[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pr[r] = lane + 64 * r < k ? raw[lane + 64 * r] : 0.0f;
-                float sum = 0.0f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int kr = k - 64 * r < 64 ? k - 64 * r : 64;                    // uniform
-                    for (int j = 0; j < kr; ++j) sum += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pr[r]), j));
-                }
-                const uint32_t first = used;
-                if (first + (uint32_t)k > T.node_cap) {
-                    if (lane == 0) atomicOr(S.overflow, 2u);
-                } else {
-                    const uint32_t e = it + 1u;
-                    for (int j = lane; j < k; j += 64) {
-                        const uint32_t cl = first + (uint32_t)j;
-                        const size_t ci = base + cl;
-                        BgState cs = lst;
-                        int d0, d1;
-                        draw_dice(seed, gid, rnd, e, (uint32_t)j, d0, d1);      // child dice frozen at creation (Q9), keyed by the GAME's iteration
-                        bg_apply_dev(cs, ws.play[j], d0, d1);
-                        store_state(&T.state[ci], cs);
-                        const float prj = raw[j] / sum;
-                        const uint32_t cm = (uint32_t)code[j] | meta_terminal_bits(cs);
-                        T.visits[ci] = 0.0f; T.value[ci] = 0.0f; T.prior[ci] = prj;
-                        T.parent[ci] = leaf; T.first_child[ci] = 0; T.meta[ci] = cm;
-                        crow_g[cl] = 0u;                                         // (crow is zeroed per move-step; kept explicit: a node is born without an evaluation)
-                        if (cl < ln) { lvis[cl] = 0.0f; lval[cl] = 0.0f; lpri[cl] = prj; lhdr[cl] = free_hdr(cm, 0u); lcrow[cl] = 0; }
-                    }
-                    const uint32_t nmeta = kDrained | ((uint32_t)k << 16) | (m0 & kMetaKeep);
-                    if (lane == 0) X.set_header(leaf, nmeta, first);
-                    used = first + (uint32_t)k;
-                    cn[SC_EXPANSIONS] += 1; cn[SC_CHILDREN] += (uint32_t)k;
-                    if ((uint32_t)k > cn[SC_MAX_CHILDREN]) cn[SC_MAX_CHILDREN] = (uint32_t)k;
-                }
-                __syncthreads();
-            }
-            if (do_backprop) {
-                if (plen) { if ((uint32_t)lane < plen) X.add(pnode, v); }
-                else if (lane == 0) { for (uint32_t i = leaf; i != kNone; i = T.parent[base + i]) X.add(i, v); }
-            }
-            if (quirks && slot == seg_first && ifl.y != 0u && lane == 0) {
-                // slots still holding the initial 0 index re-backpropagate node 0 = this root with the NN value of its state (Q14)
-                float rvis = X.vis(0), rval = X.val(0);
-                for (uint32_t i = 0; i < ifl.y; ++i) { rvis += 1.0f; rval += rv0; }
-                if (ln > 0) { lvis[0] = rvis; lval[0] = rval; }
-                T.visits[base] = rvis; T.value[base] = rval;
-            }
-            __syncthreads();
-        }
+        // ================= iteration `it` (search_iter_device.h) =================
+        search_iteration(S, R, X, pre, scratch, ifl, it, slot, lane, quirks, [&](uint32_t cl, float prj, uint32_t cm) {
+            crow_g[cl] = 0u;                                                     // (crow is zeroed per move-step; kept explicit: a node is born without an evaluation)
+            if (cl < ln) { lvis[cl] = 0.0f; lval[cl] = 0.0f; lpri[cl] = prj; lhdr[cl] = free_hdr(cm, 0u); lcrow[cl] = 0; }
+        });
         FR_STAMP(2);
         // ================= selection for iteration it + 1 (select_slot on the LDS copy), published for the other games =================
         uint32_t published = 0;
         if (it + 1 < F.iterations) {
-            uint32_t* nflag = S.iter_flags + 2 * ((size_t)seg * G.iter_cap + it + 1);
+            uint32_t* nflag = S.iter_flags + 2 * ((size_t)R.seg * G.iter_cap + it + 1);
             uint32_t node = 0, depth = 0, mine = lane == 0 ? 0u : kNone;
-            uint32_t mt = X.hdr(0), fcn = hdr_fc(mt);
+            TreeF::Hdr h = X.hdr(0);
             float nvis = X.vis(0);
             for (;;) {
-                const uint32_t k = hdr_nch(mt);
+                const uint32_t k = X.nch(h), fcn = X.fc(h);
                 if (k == 0) break;
                 const float sq = sqrtf(nvis);
                 if (k <= 64u && fcn + k <= ln) {
@@ -1398,13 +1091,9 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                     // come from its lane, not from another trip to LDS.  (a wave alone on its SIMD pays every instruction of the chain in full)
                     const bool valid = (uint32_t)lane < k;
                     const uint32_t ci = fcn + (valid ? (uint32_t)lane : 0u);
-                    const float vis = lvis[ci], val = lval[ci], pr = lpri[ci];
+                    const float vis = lvis[ci];
                     const uint32_t ch = lhdr[ci];
-                    const float q = vis == 0.0f ? 0.0f : val / vis;
-                    const float t = sq / (vis + 1.0f);
-                    const float u = c * t;
-                    const float w = u * pr;
-                    const float sc_ = q + w;
+                    const float sc_ = puct_score(vis, lval[ci], lpri[ci], sq, c);
                     const unsigned long long nans = __ballot(valid && sc_ != sc_);
                     const int lastnan = nans ? 63 - __clzll((long long)nans) : -1;
                     const bool comp = valid && sc_ == sc_ && lane > lastnan;
@@ -1414,68 +1103,28 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                     node = fcn + (uint32_t)chosen;
                     ++depth;
                     if ((uint32_t)lane == depth) mine = node;
-                    mt = (uint32_t)__builtin_amdgcn_readlane((int)ch, chosen); fcn = hdr_fc(mt);
+                    h.w = (uint32_t)__builtin_amdgcn_readlane((int)ch, chosen);
                     nvis = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, vis), chosen));
                     continue;
                 }
-                Best b{0.0f, -1};
-                int lastnan = -1;
-                for (uint32_t j = lane; j < k; j += 64) {
-                    const uint32_t ci = fcn + j;
-                    const float vis = X.vis(ci), val = X.val(ci), pr = X.pri(ci);
-                    const float q = vis == 0.0f ? 0.0f : val / vis;
-                    const float t = sq / (vis + 1.0f);
-                    const float u = c * t;
-                    const float w = u * pr;
-                    const float sc_ = q + w;
-                    if (sc_ != sc_) lastnan = (int)j;
-                    else if (b.j < 0 || !(b.s > sc_)) { b.s = sc_; b.j = (int)j; }
-                }
-                lastnan = wave_allmax_i32(lastnan);
-                if (lastnan >= 0) {                             // the sequential fold restarts after a NaN: only children after the last NaN compete
-                    b.s = 0.0f; b.j = -1;
-                    for (uint32_t j = lane; j < k; j += 64) {
-                        if ((int)j <= lastnan) continue;
-                        const uint32_t ci = fcn + j;
-                        const float vis = X.vis(ci), val = X.val(ci), pr = X.pri(ci);
-                        const float q = vis == 0.0f ? 0.0f : val / vis;
-                        const float t = sq / (vis + 1.0f);
-                        const float u = c * t;
-                        const float w = u * pr;
-                        const float sc_ = q + w;
-                        if (b.j < 0 || !(b.s > sc_)) { b.s = sc_; b.j = (int)j; }
-                    }
-                }
-                b = wave_best(b);
-                const int chosen = b.j >= 0 ? b.j : lastnan;
-                node = fcn + (uint32_t)chosen;
+                node = fcn + select_level(X, fcn, k, sq, c, lane);
                 ++depth;
                 if ((uint32_t)lane == depth) mine = node;
-                mt = X.hdr(node); fcn = hdr_fc(mt); nvis = X.vis(node);
+                h = X.hdr(node); nvis = X.vis(node);
             }
-            const uint32_t npl = depth < S.path_cap ? depth + 1u : 0u;
-            cn[SC_SELECTIONS] += 1; cn[SC_DEPTH_SUM] += depth;
-            if (mt & kMetaTerminal) {                           // a finished game: +-1 for the ROOT's player (alpha_mcts.rs:157-163)
-                const float tv = ((mt & kMetaWinnerPlus) ? 1 : -1) == root_player ? 1.0f : -1.0f;
-                if (npl) { if ((uint32_t)lane < npl) X.add(mine, tv); }
-                else if (lane == 0) { for (uint32_t i = node; i != kNone; i = T.parent[base + i]) X.add(i, tv); }
-                cn[SC_TERMINAL] += 1;
-                lterm = true;
-                if (lane == 0 && quirks && sel == kNone) published = atomicAdd(&nflag[1], 1u);
+            if (end_selection(S, R, X, node, depth, mine, h, lane)) {
+                if (lane == 0 && quirks && R.sel == kNone) published = atomicAdd(&nflag[1], 1u);
             } else {
-                lterm = false; leaf = node; plen = npl; pnode = mine;
-                leaf_meta = T.meta[base + node];                // (the header word in LDS carries no action code: the expansion of this leaf keeps it, kMetaKeep)
                 if (lane == 0) {
                     // (a 1 read from a cached line is final -- nobody clears the word within a move-step --, so only the first games to get here touch
                     // the word with an atomic: a thousand same-address atomics per iteration would queue up at ~11 ns each)
                     if (nflag[0] == 0u) published = atomicOr(&nflag[0], 1u);
-                    if (sel == kNone) F.first_sel[slot] = it + 1u;
+                    if (R.sel == kNone) F.first_sel[slot] = it + 1u;
                 }
-                sel = node;
-                lst = load_state(&T.state[base + node]);
+                R.sel = node;
             }
-            cr = lterm ? 0u : crow_of(leaf);
-            if (!lterm && at_hand(cr)) pre = net_row(cr);       // (in flight while the selection is published)
+            cr = R.lterm ? 0u : crow_of(R.leaf);
+            if (!R.lterm && at_hand(cr)) pre = net_row(cr);       // (in flight while the selection is published)
         }
         ++it;
         __syncthreads();
@@ -1489,15 +1138,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
         FR_STAMP(3); FR_COUNT(9, 1);
         if (it >= F.iterations) break;
     }
-    // ---- the record for the next launch (and for whoever reads the slot after the search) ----
-    if (lane == 0) {
-        S.leaf_term[slot] = lterm ? 1 : 0; S.leaf[slot] = leaf; S.sel[slot] = sel; S.leaf_meta[slot] = leaf_meta;
-        S.sel_value[slot] = sel_value; S.path_len[slot] = (uint8_t)plen;
-        T.used[slot] = used;
-        if (slot == seg_first) S.counters[(size_t)seg * CNT_COUNT + CNT_NN_EVALS] = evals;
-        store_state(&S.eval_states[slot], lst);
-    }
-    if ((uint32_t)lane < plen) S.path[(size_t)slot * kPathCap + lane] = pnode;
+    R.store(T, S, slot, lane);
     const bool done = it >= F.iterations;
     uint32_t nw = 0;
     const bool dem = !done && !stalled && !have;
@@ -1506,7 +1147,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
         // the search's own selection rule run ahead on a scratch copy of visits / value; an unknown evaluation counts as 0, a known one as
         // its value, a finished game as +-1 for the root's player -- end on, in the order they are found (= the order the search will want them) ----
         uint32_t* wl = F.wish + (size_t)slot * kFreeWish;
-        if (dem) { if (lane == 0) wl[0] = leaf; nw = 1; }
+        if (dem) { if (lane == 0) wl[0] = R.leaf; nw = 1; }
         // (the launch lasts as long as its busiest game: one that ran its full share of iterations -- it is ahead of the others and the rows it was
         // granted served it well -- looks for fewer candidates: every iteration it ran takes two virtual descents off its budget)
         uint32_t want0 = F.cand_max < kFreeWish - 1u ? F.cand_max : kFreeWish - 1u;
@@ -1519,7 +1160,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
         const uint32_t want = few ? want0 : (want0 > ran / 2u + 1u ? want0 - ran / 2u : (want0 ? 1u : 0u));
         uint32_t ncand = 0;
         if (want > 0 && steps_max > 0) {
-            const uint32_t nu = used < ln ? used : ln;
+            const uint32_t nu = R.used < ln ? R.used : ln;
             for (uint32_t i0 = 0; i0 < nu; i0 += 256) {             // four rounds of reads in flight before the first write, as in the staging above
                 float a[4], b[4];
 #pragma unroll
@@ -1528,10 +1169,10 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                 for (int u = 0; u < 4; ++u) { const uint32_t i = i0 + 64u * u + (uint32_t)lane; if (i < nu) { vvis[i] = a[u]; vval[i] = b[u]; } }
             }
             __syncthreads();
-            const uint32_t demanded = dem ? leaf : kNone;
+            const uint32_t demanded = dem ? R.leaf : kNone;
             uint32_t fruitless = 0;
-            const uint32_t h0 = X.hdr(0), k0 = hdr_nch(h0), fc0 = hdr_fc(h0);
-            const bool resident = used <= ln && k0 >= 1u && k0 <= 64u;       // (uniform)
+            const uint32_t h0 = X.hdr(0).w, k0 = hdr_nch(h0), fc0 = hdr_fc(h0);
+            const bool resident = R.used <= ln && k0 >= 1u && k0 <= 64u;       // (uniform)
             // The usual case -- the whole tree is in LDS, the root's children fit one per lane --: the same rule on the same numbers with the
             // round trips taken out of the chain.  The root level lives in registers (lane j keeps child j, patched on every virtual visit); a
             // level below reads everything about a child in ONE trip (statistics, header, evaluation), so the chosen child's header and
@@ -1556,8 +1197,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                     int j0;
                     {
                         const float sq = __builtin_amdgcn_sqrtf(r_vis);
-                        const float q = c_vis == 0.0f ? 0.0f : c_val * __builtin_amdgcn_rcpf(c_vis);
-                        const float sc_ = q + (c * (sq * __builtin_amdgcn_rcpf(c_vis + 1.0f))) * c_pri;
+                        const float sc_ = puct_score_approx(c_vis, c_val, c_pri, sq, c);
                         j0 = last_max(rc && sc_ == sc_, sc_, k0);
                     }
                     uint32_t node = fc0 + (uint32_t)j0, depth = 1, mine = kNone, mt = h0;
@@ -1574,8 +1214,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                             const uint32_t ci = fcn + (valid ? (uint32_t)lane : 0u);
                             const float vis = vvis[ci], val = vval[ci], pr = lpri[ci], cv = lcval[ci];
                             const uint32_t h = lhdr[ci], cr = lcrow[ci];
-                            const float q = vis == 0.0f ? 0.0f : val * __builtin_amdgcn_rcpf(vis);
-                            const float sc_ = q + (c * (sq * __builtin_amdgcn_rcpf(vis + 1.0f))) * pr;
+                            const float sc_ = puct_score_approx(vis, val, pr, sq, c);
                             const int lw = last_max(valid && sc_ == sc_, sc_, k);
                             node = fcn + (uint32_t)lw;
                             hn = rl_u(h, lw); ncr = rl_u(cr, lw); pvis = rl_f(vis, lw); pval = rl_f(val, lw); ncv = rl_f(cv, lw);
@@ -1587,9 +1226,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                         Best b{0.0f, -1};                           // (more than 64 children -- rare --: the general fold, then one more trip for the chosen child)
                         for (uint32_t j = lane; j < k; j += 64) {
                             const uint32_t ci = fcn + j;
-                            const float vis = vvis[ci], val = vval[ci];
-                            const float q = vis == 0.0f ? 0.0f : val * __builtin_amdgcn_rcpf(vis);
-                            const float sc_ = q + (c * (sq * __builtin_amdgcn_rcpf(vis + 1.0f))) * lpri[ci];
+                            const float sc_ = puct_score_approx(vvis[ci], vval[ci], lpri[ci], sq, c);
                             if (sc_ == sc_ && (b.j < 0 || !(b.s > sc_))) { b.s = sc_; b.j = (int)j; }
                         }
                         b = wave_best(b);
@@ -1601,7 +1238,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                     }
                     float x = 0.0f;
                     bool fresh = false;
-                    if (mt & kMetaTerminal) x = ((mt & kMetaWinnerPlus) ? 1 : -1) == root_player ? 1.0f : -1.0f;
+                    if (mt & kMetaTerminal) x = finished_value(mt, R.root_player);
                     else if (at_hand(ncr)) x = ncv;
                     else if (!(mt & kDrained) && node != demanded) fresh = __ballot((uint32_t)lane < ncand && my_cand == node) == 0ull;
                     if (fresh) { if ((uint32_t)lane == ncand) my_cand = node; if (lane == 0) wl[nw + ncand] = node; ++ncand; fruitless = 0; } else ++fruitless;
@@ -1613,36 +1250,15 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
                 }
             } else
             for (uint32_t step = 0; step < steps_max && ncand < want && fruitless < 8; ++step) {
-                uint32_t node = 0, depth = 0, mine = lane == 0 ? 0u : kNone, mt = 0;
-                for (;;) {
-                    mt = X.hdr(node);
-                    const uint32_t k = hdr_nch(mt);
-                    if (k == 0) break;
-                    const uint32_t fcn = hdr_fc(mt);
-                    // (a prediction, not the search: the hardware's approximate reciprocal and square root will do)
-                    const float sq = __builtin_amdgcn_sqrtf(node < nu ? vvis[node] : T.visits[base + node]);
-                    Best b{0.0f, -1};
-                    for (uint32_t j = lane; j < k; j += 64) {
-                        const uint32_t ci = fcn + j;
-                        const float vis = ci < nu ? vvis[ci] : T.visits[base + ci], val = ci < nu ? vval[ci] : T.value[base + ci];
-                        const float q = vis == 0.0f ? 0.0f : val * __builtin_amdgcn_rcpf(vis);
-                        const float sc_ = q + (c * (sq * __builtin_amdgcn_rcpf(vis + 1.0f))) * X.pri(ci);
-                        if (sc_ == sc_ && (b.j < 0 || !(b.s > sc_))) { b.s = sc_; b.j = (int)j; }
-                    }
-                    b = wave_best(b);
-                    node = fcn + (uint32_t)(b.j >= 0 ? b.j : (int)k - 1);
-                    ++depth;
-                    if ((uint32_t)lane == depth) mine = node;
-                    if (depth >= 63) break;
-                }
-                const uint32_t cr = crow_of(node);
+                const VirtualDescent d = virtual_descent<false>(X, vvis, vval, nu, c, lane);
+                const uint32_t node = d.node, cr = crow_of(node);
                 float x = 0.0f;
                 bool fresh = false;
-                if (mt & kMetaTerminal) x = ((mt & kMetaWinnerPlus) ? 1 : -1) == root_player ? 1.0f : -1.0f;
+                if (d.bits & kMetaTerminal) x = finished_value(d.bits, R.root_player);
                 else if (at_hand(cr)) x = node < ln ? lcval[node] : cval_g[node];
-                else if (!(mt & kDrained) && node != demanded) fresh = __ballot((uint32_t)lane < ncand && cand[lane] == node) == 0ull;
+                else if (!(d.bits & kDrained) && node != demanded) fresh = __ballot((uint32_t)lane < ncand && cand[lane] == node) == 0ull;
                 if (fresh) { if (lane == 0) { cand[ncand] = node; wl[nw + ncand] = node; } ++ncand; fruitless = 0; } else ++fruitless;
-                if ((uint32_t)lane <= depth && mine < nu) { vvis[mine] += 1.0f; vval[mine] += x; }
+                virtual_visit(d, vvis, vval, nu, x, lane);
                 __syncthreads();
                 FR_COUNT(11, 1);
             }
@@ -1651,7 +1267,7 @@ __global__ __launch_bounds__(64) void k_free(Tree T, Slots S, Segs G, uint32_t n
     }
     if (lane == 0) {
         F.wish_n[slot] = nw | (it << 8) | (dem ? 0x80000000u : 0u);
-        store_counters(S, slot, cn);
+        store_counters(S, slot, R.cn);
     }
     FR_STAMP(4);
 #ifdef DIEE_TAIL_STAMPS

@@ -257,18 +257,22 @@ def test_compacted_evaluation_changes_nothing_but_the_row_count(oracle, monkeypa
     assert a["stats"]["nn_rows"] == a["stats"]["nn_evals"] - a["stats"]["terminal_hits"]      # one row saved per terminal selection
 
 
-@pytest.mark.parametrize("cap", ["1", "2", "3"])
-def test_parent_walk_backpropagation_equals_the_recorded_path(oracle, monkeypatch, cap):
+@pytest.mark.parametrize("cap,tail", [pytest.param("1", False, id="1"), pytest.param("2", False, id="2"), pytest.param("3", False, id="3"),
+                                      pytest.param("1", True, id="tail-1"), pytest.param("2", True, id="tail-2")])
+def test_parent_walk_backpropagation_equals_the_recorded_path(oracle, monkeypatch, cap, tail):
     """k_expand backpropagates over the root-to-leaf path its selection recorded (one lane per level); selections deeper
     than the record fall back to walking the parent indices.  option path_cap lowers the record so that ordinary searches
     reach the fallback in the stale-slot re-backpropagation (Q14), the terminal-leaf backpropagation of the descent and the
-    ordinary one: results and counters identical to the default"""
+    ordinary one: results and counters identical to the default.  64 roots run the iterations on k_free; `tail`: the first 6
+    late and the first 6 mid-game roots of those, 12 games, which the default dispatch gives to k_tail -- the same three
+    fallbacks of the shared iteration (search_iter_device.h) on k_tail's accessor"""
     import diee_amd
     walk = oracle.random_walk_states(91, 60)
     late = walk[walk["off"].max(axis=1) >= 11][:24]
-    states = np.concatenate([late, walk[150:150 + 5 * 40:5]])
-    n = len(states)
-    _, gcfg = cfgs(oracle, 48)
+    mid = walk[150:150 + 5 * 40:5]
+    states = np.concatenate([late[:6], mid[:6]]) if tail else np.concatenate([late, mid])
+    n, iters = len(states), 48
+    _, gcfg = cfgs(oracle, iters)
     gids = np.arange(n, dtype=np.uint32); rds = np.arange(n, dtype=np.uint32) % 7
     res = []
     for c in (None, cap):
@@ -277,10 +281,17 @@ def test_parent_walk_backpropagation_equals_the_recorded_path(oracle, monkeypatc
         res.append(e.alpha_mcts_parallel(states, gcfg, SEED, 5, gids, rds, ref_quirks=True))
         e.close()
     a, b = res
+    print(f"[parent walk] {n} roots, cap {cap}: tail_iterations {a['stats']['tail_iterations']} / {b['stats']['tail_iterations']}, terminal_hits "
+          f"{a['stats']['terminal_hits']}, depth_sum {a['stats']['depth_sum']}, selections {a['stats']['selections']}")
     assert a["probs"].tobytes() == b["probs"].tobytes() and (a["root_visits"] == b["root_visits"]).all()
     for key in ("nn_evals", "expansions", "children", "terminal_hits", "depth_sum", "selections", "max_children"):
         assert a["stats"][key] == b["stats"][key], key
-    assert a["stats"]["terminal_hits"] > 0 and a["stats"]["depth_sum"] > 2 * a["stats"]["selections"]     # deeper than every cap tried
+    if tail:
+        assert n == 12 and a["stats"]["tail_iterations"] == iters and b["stats"]["tail_iterations"] == iters    # the kernel meant is the one that ran
+        assert a["stats"]["terminal_hits"] > 0
+        assert a["stats"]["depth_sum"] > int(cap) * a["stats"]["selections"]                                   # the selections really are deeper than the record
+    else:
+        assert a["stats"]["terminal_hits"] > 0 and a["stats"]["depth_sum"] > 2 * a["stats"]["selections"]     # deeper than every cap tried
 
 
 @pytest.mark.parametrize("n", [5, 20, 24, 40, 80])
