@@ -10,6 +10,7 @@ reference's tests:
     alpha_mcts_parallel + get_prob_tensor_parallel (src/mcts/alpha_mcts.rs:91, utils.rs:42)
                                                   -> Engine.alpha_mcts_parallel
     AlphaZero::self_play_parallel (src/alphazero/alpha_parallel.rs:101) -> Engine.self_play_parallel
+    play (src/versus.rs:160-268)                  -> arena / Engine.arena (die-e_amd/versus.py: play_device)
 
 There is no CPU fallback: the library must load and a GPU must be present, otherwise the
 constructor raises.  Import with importlib.import_module("die-e_amd") (the directory name is
@@ -29,6 +30,7 @@ NO_MOVE = -2
 GAME_TTT, GAME_BACKGAMMON = 0, 1
 FLAG_REF_QUIRKS = 1
 FLAG_INVARIANT_NN = 2
+AGENT_RANDOM, AGENT_MODEL = 0, 1                         # DIEE_AGENT_*: the agents of Engine.arena
 BAND_BOUNDS = (16, 32, 64, 128, 256, 512, 928, 1024)     # DIEE_BANDS: upper bounds of Stats.band_* (the ninth band is everything above)
 
 OK, ERR_ARG, ERR_HIP, ERR_NO_WEIGHTS, ERR_CAPACITY, ERR_UNSUPPORTED = range(6)
@@ -46,7 +48,7 @@ assert TTT_STATE.itemsize == 32
 EXPORTS = [
     "diee_create", "diee_destroy", "diee_last_error", "diee_version", "diee_set_option", "diee_get_option", "diee_device_pci_bus_id", "diee_weights_count",
     "diee_random_weights", "diee_load_weights", "diee_nn_forward", "diee_mcts_batch", "diee_self_play",
-    "diee_self_play_multi", "diee_self_play_refill", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
+    "diee_self_play_multi", "diee_self_play_refill", "diee_arena", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
     "diee_train_conv3x3", "diee_train_im2col3x3",
     "diee_train_scratch_floats", "diee_train_bn_relu_fwd", "diee_train_bn_relu_bwd", "diee_train_colsum",
     "diee_train_set_bn_coop", "diee_train_bn_coop_timeouts",
@@ -98,6 +100,12 @@ class Stats(C.Structure):
 class Fragments(C.Structure):
     _fields_ = [("n", C.c_uint32), ("outcome", C.POINTER(C.c_int8)), ("ps", C.POINTER(C.c_float)),
                 ("state", C.POINTER(C.c_float)), ("game", C.POINTER(C.c_uint32))]
+
+
+class ArenaResult(C.Structure):
+    """diee_arena_result"""
+    _fields_ = [("wins_p1", C.c_uint32), ("wins_p2", C.c_uint32), ("draws", C.c_uint32), ("rounds", C.c_uint32),
+                ("illegal_decodes", C.c_uint64), ("seconds", C.c_double)]
 
 
 class DevLaunch(C.Structure):
@@ -152,6 +160,7 @@ def load_library(path=None):
     L.diee_self_play.argtypes = [vp, u32, u32, vp, f32, u64, u32, u32, vp, vp]; L.diee_self_play.restype = C.c_int
     L.diee_self_play_multi.argtypes = [vp, vp, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_multi.restype = C.c_int
     L.diee_self_play_refill.argtypes = [vp, vp, u32, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_refill.restype = C.c_int
+    L.diee_arena.argtypes = [vp, C.c_int, vp, C.c_int, u32, vp, f32, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]; L.diee_arena.restype = C.c_int
     L.diee_set_invariant_nn.argtypes = [vp, C.c_int]; L.diee_set_invariant_nn.restype = C.c_int
     L.diee_train_pack_conv3x3.argtypes = [vp, vp, C.c_int, vp]; L.diee_train_pack_conv3x3.restype = C.c_int
     L.diee_train_pack_conv3x3_multi.argtypes = [C.POINTER(vp), C.c_int, vp, vp]; L.diee_train_pack_conv3x3_multi.restype = C.c_int
@@ -477,6 +486,38 @@ class Engine:
         self._chk(self._L.diee_self_play_refill(self._h, C.byref(bt), K, int(width), C.byref(cfg), temperature, flags, max_steps,
                                                 C.byref(frs) if fetch else None, C.byref(sts)))
         return self._take_batches(frs, sts, fetch, copy)
+
+    def arena(self, agent1, other, agent2, n_games, cfg, temperature=1.25, seed=0xD1EE0001, round_limit=400, max_rounds=0,
+              ref_quirks=True, invariant_nn=False):
+        """arena() below with this engine as player 1"""
+        return arena(self, agent1, other, agent2, n_games, cfg, temperature, seed, round_limit, max_rounds, ref_quirks, invariant_nn)
+
+
+def arena(engine1, agent1, engine2, agent2, n_games, cfg, temperature=1.25, seed=0xD1EE0001, round_limit=400, max_rounds=0,
+          ref_quirks=True, invariant_nn=False):
+    """play() of versus.rs:160-268 in one engine call (diee_arena).  engine1 is player 1 (side -1 in every game) and hosts the call,
+    engine2 (an Engine on the same device, engine1 again, or None for a Random agent) lends player 2's network; engine1 may be None
+    for a Random agent, then engine2 hosts.  agent1 / agent2: AGENT_MODEL | AGENT_RANDOM.  -> dict(wins_p1, wins_p2, draws, rounds,
+    illegal_decodes, seconds, winner int8 [n], retired_round uint32 [n] (0xFFFFFFFF: still alive, max_rounds), retired_side int8 [n],
+    initial_states, final_states, stats [per player]); raises if a sampled action did not decode to a valid move (versus.rs:229
+    panics)"""
+    host = engine1 if engine1 is not None else engine2
+    if host is None:
+        raise ValueError("the arena needs an engine")
+    n = int(n_games)
+    winner = np.zeros(n, dtype=np.int8); rside = np.zeros(n, dtype=np.int8); rround = np.zeros(n, dtype=np.uint32)
+    init = np.zeros(n, dtype=BG_STATE); final = np.zeros(n, dtype=BG_STATE)
+    res = ArenaResult(); sts = (Stats * 2)()
+    flags = (FLAG_REF_QUIRKS if ref_quirks else 0) | (FLAG_INVARIANT_NN if invariant_nn else 0)
+    host._chk(host._L.diee_arena(None if engine1 is None else engine1._h, int(agent1), None if engine2 is None else engine2._h, int(agent2),
+                                 n, C.byref(cfg), temperature, seed, int(round_limit), int(max_rounds), flags, C.byref(res),
+                                 winner.ctypes.data, rround.ctypes.data, rside.ctypes.data, init.ctypes.data, final.ctypes.data,
+                                 C.byref(sts)))
+    if res.illegal_decodes:
+        raise DieeError(ERR_CAPACITY, f"decoded action is not a valid move ({res.illegal_decodes} illegal decodes)")
+    return {"wins_p1": res.wins_p1, "wins_p2": res.wins_p2, "draws": res.draws, "rounds": res.rounds,
+            "illegal_decodes": res.illegal_decodes, "seconds": res.seconds, "winner": winner, "retired_round": rround,
+            "retired_side": rside, "initial_states": init, "final_states": final, "stats": [sts[0].as_dict(), sts[1].as_dict()]}
 
 
 # ---- LearnableGame for TicTacToe (src/tictactoe/mod.rs), host functions of the C ABI -------------------------------------

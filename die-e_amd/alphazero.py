@@ -583,6 +583,8 @@ class AlphaZero:
         from .versus import Agent, Player, play
         if self.game is TICTACTOE:
             from .versus import play_tictactoe as play
+        elif os.environ.get("DIEE_ARENA") == "device":                          # every round on the device (diee_arena): the same result
+            from .versus import play_device as play
         mdir = os.path.join(self.root, "models", self.game.name)
         best = os.path.join(mdir, "best_model.npy")
         if not os.path.exists(best) and os.path.exists(os.path.join(mdir, "best_model.ot")):

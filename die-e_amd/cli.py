@@ -171,8 +171,12 @@ def main(argv=None):
             e.load_weights(load_model(path))                                                  # .npy blob or die-e's .ot archive
             return e
         m1, m2 = model(args.model_path_one), model(args.model_path_two)
-        res = play(Player(a1, m1), Player(a2, m2), mcts_config_from(conf), float(conf["temperature"]),
-                   rules=EngineRules(m1 or m2 or eng))
+        if os.environ.get("DIEE_ARENA") == "device":                                          # every round on the device (diee_arena): the same result
+            from .versus import play_device
+            res = play_device(Player(a1, m1), Player(a2, m2), mcts_config_from(conf), float(conf["temperature"]), engine=eng)
+        else:
+            res = play(Player(a1, m1), Player(a2, m2), mcts_config_from(conf), float(conf["temperature"]),
+                       rules=EngineRules(m1 or m2 or eng))
         print(f"{res}\n Saving games...")
         for g in res.games:
             save_game(g, args.output_path)

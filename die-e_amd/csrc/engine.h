@@ -119,6 +119,10 @@ public:
                          uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats);
     void self_play_refill(const diee_batch* batches, uint32_t n_batches, uint32_t width, const diee_mcts_cfg* cfg, float temperature,
                           uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats);
+    // the arena (versus.rs:160-318): this ctx hosts the call; net1 / net2 = the networks of the two players' ctxs (null for a Random agent)
+    void arena(NetWeights* net1, int agent1, NetWeights* net2, int agent2, uint32_t n_games, const diee_mcts_cfg* cfg, float temperature,
+               uint64_t seed, uint32_t round_limit, uint32_t max_rounds, uint32_t flags, diee_arena_result* res, int8_t* winner,
+               uint32_t* retired_round, int8_t* retired_side, diee_bg_state* initial_states, diee_bg_state* final_states, diee_stats* stats);
     uint32_t refill_areas = 0;       // record areas the last self_play_refill allocated (read-only option refill_record_areas)
 
     int device;

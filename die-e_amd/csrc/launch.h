@@ -122,6 +122,14 @@ void launch_refill_admit(hipStream_t st, const Games& Gm, const uint32_t* n_live
 void launch_deliver_scan(hipStream_t st, const Games& Gm, const Segs& G, uint32_t n_live, uint32_t step, DeliverEvent* ev, uint32_t* summary);
 void launch_deliver_copy(hipStream_t st, const Games& Gm, const Segs& G, const DeliverEvent* ev, uint32_t n_ev, uint32_t r0, uint32_t r1,
                          const DeliverOut& out);
+// arena_kernels.hip (search_types.h, Arena)
+void launch_arena_init(hipStream_t st, const Arena& A, unsigned long long seed);
+// compacts the live list (n_live entries) and splits it by side to move; A.words[AW_COUNT0 .. AW_LIVE] = the two counts and their sum
+void launch_arena_split(hipStream_t st, const Arena& A, uint32_t n_live);
+// the n games of side `side`'s list -> slots 0 ... n - 1 (roots, game_id = game index, round), one batch spanning them
+void launch_arena_gather(hipStream_t st, const Arena& A, const Slots& S, const Segs& G, uint32_t side, uint32_t n, uint32_t round);
+// the moves of the n games of P.side's list: sampled from their searched roots (slot = position in the list) or picked among the legal plays
+void launch_arena_move(hipStream_t st, const Tree& T, const Arena& A, uint32_t n, const ArenaParams& P, uint32_t* overflow);
 constexpr uint32_t kRootIteration = 0xFFFFFFFFu;
 constexpr uint32_t kNoNextIteration = 0xFFFFFFFEu;
 

@@ -99,4 +99,56 @@ __device__ __forceinline__ void grow_slot(const Tree& T, const Slots& S, const S
     if (lane == 0) S.grow_k[slot] = (uint32_t)k;
 }
 
+// The move a driver samples from a searched root (self-play: alpha_parallel.rs:164-166,200; the arena: versus.rs:281-299), by ONE
+// wave that is its whole workgroup: the get_prob_tensor_parallel row (child visits / their f32 sum in child order), pow_(1 / T) not
+// renormalised (Q17) -- left in row[1352] (LDS) for the caller --, then weighted_select_tensor_idx (alphazero.rs:129-137: rand
+// WeightedIndex over f64 weights) with the uniform of (seed, gid, round, kTagSample).  k = the root's children (1 ... 256), fc = its
+// first child.  Returns the action code, the same in every lane; *total_out = the f64 sum of the weights (0 or NaN: an all-zero row).
+__device__ __forceinline__ uint32_t sample_root_move(const Tree& T, size_t base, uint32_t k, uint32_t fc, float* row, int lane, float inv_temperature,
+                                                     unsigned long long seed, uint32_t gid, uint32_t round, double* total_out = nullptr) {
+    for (int a = lane; a < 1352; a += 64) row[a] = 0.0f;
+    // the children's visits and codes in one round of loads (k <= 256: four per lane); the row sum in child order on values broadcast
+    // from their lanes (the same chain of f32 additions in every lane)
+    float vis[4]; uint32_t cod[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const uint32_t j = lane + 64 * r;
+        vis[r] = j < k ? T.visits[base + fc + j] : 0.0f;
+        cod[r] = j < k ? T.meta[base + fc + j] & 0xFFFFu : 0u;
+    }
+    float sum = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int kr = (int)k - 64 * r < 64 ? (int)k - 64 * r : 64;                    // uniform
+        for (int j = 0; j < kr; ++j) sum += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, vis[r]), j));
+    }
+    __syncthreads();                                            // (the zeroed row before the scattered weights)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if ((uint32_t)(lane + 64 * r) < k) row[cod[r]] = det_powf(vis[r] / sum, inv_temperature);
+    __syncthreads();
+    // The f64 sums run over all 1352 weights in index order; at most k of them are not +0.0, and x + 0.0 == x exactly, so only those
+    // are added, in index order: one ballot per 64 codes finds them (1352 dependent f64 adds from LDS, twice, were ~85 us per move-step).
+    unsigned long long nzm[22];
+#pragma unroll
+    for (int q = 0; q < 22; ++q) nzm[q] = __ballot(64 * q + lane < 1352 && row[64 * q + lane] != 0.0f);
+    double total = 0.0;
+#pragma unroll
+    for (int q = 0; q < 22; ++q)
+        for (unsigned long long m = nzm[q]; m; m &= m - 1) total += (double)row[64 * q + __builtin_ctzll(m)];
+    const double x = draw_uniform(seed, gid, round, kTagSample, 0u) * total;
+    double cum = 0.0;
+    int pick = -1, last_nz = 0;
+#pragma unroll
+    for (int q = 0; q < 22; ++q)
+        for (unsigned long long m = nzm[q]; m && pick < 0; m &= m - 1) {
+            const int a = 64 * q + __builtin_ctzll(m);
+            last_nz = a;
+            cum += (double)row[a];
+            if (cum > x) pick = a;
+        }
+    if (total_out) *total_out = total;
+    return (uint32_t)(pick >= 0 ? pick : last_nz);              // (uniform: every lane ran the same chain)
+}
+
 }  // namespace diee

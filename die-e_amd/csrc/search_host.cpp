@@ -71,6 +71,11 @@ struct SearchBufs {
     DevBuf<uint32_t> rf_area, rf_free;
     DevBuf<float> noise_tab;
     uint32_t noise_rows = 0;                                   // move-steps noise_tab holds in this call; 0: not a refill call
+    // the arena (search_types.h, Arena)
+    DevBuf<BgState> ar_state, ar_initial;
+    DevBuf<uint8_t> ar_alive;
+    DevBuf<int8_t> ar_winner, ar_side;
+    DevBuf<uint32_t> ar_round, ar_live, ar_list, ar_words;
     // output delivery: this step's flushes (double-buffered: the copy stream reads step s's list while step s + 1's is written),
     // one staging buffer (the copy stream runs gather -> copies out -> next gather in order), the stream and its guards
     DevBuf<DeliverEvent> dl_events[2];
@@ -887,6 +892,126 @@ void Engine::self_play_run(const diee_batch* batches, uint32_t n_batches, uint32
     }
     if (deliver)
         for (uint32_t k = 0; k < n_batches; ++k) fb[k].release(&outs[k]);
+}
+
+// play() of versus.rs:160-268 with both agents' turns on the device.  Per round: ONE device->host read (the two sides' counts and
+// the games alive, k_arena_split), then for each side with games to move { gather its list into the slots, search it with that
+// player's network (mcts_run, unchanged: e.net points at it for the duration), play its moves }.  Both sides' trees share the slot
+// space, so a side's moves are played before the other side searches; a game is in one list only, which makes that the same as the
+// reference's "collect the actions of both, then apply".
+void Engine::arena(NetWeights* net1, int agent1, NetWeights* net2, int agent2, uint32_t n_games, const diee_mcts_cfg* cfg, float temperature,
+                   uint64_t seed, uint32_t round_limit, uint32_t max_rounds, uint32_t flags, diee_arena_result* res, int8_t* winner,
+                   uint32_t* retired_round, int8_t* retired_side, diee_bg_state* initial_states, diee_bg_state* final_states, diee_stats* stats) {
+    HIPCHK(hipSetDevice(device));
+    if (res) memset(res, 0, sizeof *res);
+    if (stats) memset(stats, 0, sizeof(diee_stats) * 2);
+    if (n_games == 0 || round_limit == 0) throw EngineError(DIEE_ERR_ARG, "the arena needs n_games >= 1 and round_limit >= 1");
+    if (n_games > (1u << 22)) throw EngineError(DIEE_ERR_ARG, "too many games in flight");
+    NetWeights* const nets[2] = {net1, net2};
+    const int agents[2] = {agent1, agent2};
+    for (int s = 0; s < 2; ++s) {
+        if (agents[s] != DIEE_AGENT_RANDOM && agents[s] != DIEE_AGENT_MODEL) throw EngineError(DIEE_ERR_ARG, "agent: DIEE_AGENT_RANDOM or DIEE_AGENT_MODEL");
+        if (agents[s] == DIEE_AGENT_MODEL && (!nets[s] || !nets[s]->loaded)) throw EngineError(DIEE_ERR_NO_WEIGHTS, "diee_load_weights has not been called for a Model agent's ctx");
+    }
+    reserve_search(*this, n_games, cfg->iterations);
+    SearchBufs& B = *search;
+    B.noise_rows = 0;
+    // the two networks for the duration of the call: no sampled timing (as in mcts_batch), DIEE_FLAG_INVARIANT_NN, activations for n_games rows
+    struct NetScope {
+        Engine& e; NetWeights* own; NetWeights* w[2] = {nullptr, nullptr}; bool inv[2]; int se[2];
+        ~NetScope() { for (int s = 0; s < 2; ++s) if (w[s]) { w[s]->invariant = inv[s]; w[s]->sample_every = se[s]; } e.net = own; }
+    } scope{*this, net};
+    for (int s = 0; s < 2; ++s) {
+        if (agents[s] != DIEE_AGENT_MODEL || (s == 1 && scope.w[0] == nets[1])) continue;
+        NetWeights* w = nets[s];
+        scope.w[s] = w; scope.inv[s] = w->invariant; scope.se[s] = w->sample_every;
+        if (flags & DIEE_FLAG_INVARIANT_NN) w->invariant = true;
+        w->sample_every = 0; w->cur_step = 0;
+        net = w;
+        nn_reserve(*this, (int)n_games);
+    }
+    B.ar_state.ensure(n_games); B.ar_initial.ensure(n_games); B.ar_alive.ensure(n_games); B.ar_winner.ensure(n_games); B.ar_side.ensure(n_games);
+    B.ar_round.ensure(n_games); B.ar_live.ensure(n_games); B.ar_list.ensure(2 * (size_t)n_games); B.ar_words.ensure(AW_COUNT);
+    const Arena A{B.ar_state.p, B.ar_initial.p, B.ar_alive.p, B.ar_winner.p, B.ar_round.p, B.ar_side.p, B.ar_live.p, B.ar_list.p, B.ar_words.p, n_games};
+    const Segs G = segs_view(B, 1);
+    // every search is ONE batch (one alpha_mcts_parallel call) of the call's seed; its counters collect in row 0 of the counter table, the
+    // two players' running totals are kept in rows 1 and 2
+    const std::vector<diee_batch> one{{n_games, 0u, seed}};
+    upload_segments(*this, one);
+    unsigned long long* const cnt0 = B.counters.p;
+    auto acc = [&](int s) { return B.counters.p + (size_t)(1 + s) * CNT_COUNT; };
+    B.tl_iterations = B.tl_launched = B.tl_with_rows = B.tl_spec_rows = B.tl_syncs = 0;
+    uint32_t tl_need[2] = {0, 0}, fr_need[2] = {0, 0};               // launches each side's previous search needed (size the first chunk of the next)
+    HIPCHK(hipMemsetAsync(B.step_log.p, 0, sizeof(unsigned long long) * 2 * kStepLog, stream));
+    launch_arena_init(stream, A, seed);
+    HIPCHK(hipGetLastError());
+    sync();
+    const auto t0 = std::chrono::steady_clock::now();
+    const float inv_t = (float)(1.0 / (double)temperature);
+    uint32_t n_live = n_games, round = 0;
+    uint64_t searches[2] = {0, 0}, bands[2][DIEE_BANDS] = {};
+    static const uint32_t kBandBounds[DIEE_BANDS - 1] = {16, 32, 64, 128, 256, 512, 928, 1024};
+    for (;;) {                                                          // versus.rs:191
+        launch_arena_split(stream, A, n_live);                         // :195-196
+        HIPCHK(hipGetLastError());
+        d2h(B.live_host, A.words + AW_COUNT0, 3);
+        sync();
+        const uint32_t cnt[2] = {B.live_host[0], B.live_host[1]};
+        n_live = B.live_host[2];
+        if (n_live == 0 || (max_rounds != 0 && round >= max_rounds)) break;
+        if (opt.trace_steps) fprintf(stderr, "[diee] arena round %u: %u + %u games to move\n", round, cnt[0], cnt[1]);
+        for (uint32_t s = 0; s < 2; ++s) {
+            if (!cnt[s]) continue;
+            uint32_t b = 0;
+            while (b < DIEE_BANDS - 1 && cnt[s] > kBandBounds[b]) ++b;
+            ++bands[s][b];
+            if (agents[s] == DIEE_AGENT_MODEL) {                        // :279-283
+                net = nets[s];
+                draw_noise(B, (int)s, one, 2 * round + s, cfg->dir_alpha);      // (buffer s was last read by round - 1's search: complete, the split's sync is behind it)
+                launch_arena_gather(stream, A, slots_view(*this, B), G, s, cnt[s], round);
+                HIPCHK(hipMemcpyAsync(cnt0, acc((int)s), sizeof(unsigned long long) * CNT_COUNT, hipMemcpyDeviceToDevice, stream));
+                B.cur_step = round;
+                B.tl_prev_need = tl_need[s]; B.fr_prev_need = fr_need[s];
+                mcts_run(*this, cnt[s], 1, *cfg, (int)s, flags);
+                // (a starved hand-over drops the cluster / pair tower of THIS player's network for the rest of the process, by the hosting ctx's options)
+                if (cluster_starved(*this)) {                           // rare: repeat this search on the per-layer kernels, before the moves are played
+                    HIPCHK(hipMemcpyAsync(cnt0, acc((int)s), sizeof(unsigned long long) * CNT_COUNT, hipMemcpyDeviceToDevice, stream));
+                    mcts_run(*this, cnt[s], 1, *cfg, (int)s, flags);
+                }
+                tl_need[s] = B.tl_prev_need; fr_need[s] = B.fr_prev_need;
+                HIPCHK(hipMemcpyAsync(acc((int)s), cnt0, sizeof(unsigned long long) * CNT_COUNT, hipMemcpyDeviceToDevice, stream));
+                ++searches[s];
+            }
+            const ArenaParams P{seed, round, round_limit, inv_t, s, (uint32_t)agents[s]};
+            launch_arena_move(stream, tree_view(B), A, cnt[s], P, flags_dev.p);      // :220-266
+        }
+        HIPCHK(hipGetLastError());
+        ++round;                                                        // :219
+    }
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    check_overflow();
+    uint32_t words[AW_COUNT];
+    d2h(words, A.words, (size_t)AW_COUNT);
+    if (winner) d2h(winner, A.winner, (size_t)n_games);
+    if (retired_round) d2h(retired_round, A.retired_round, (size_t)n_games);
+    if (retired_side) d2h(retired_side, A.retired_side, (size_t)n_games);
+    if (initial_states) d2h((uint8_t*)initial_states, (const uint8_t*)A.initial, (size_t)n_games * 32);
+    if (final_states) d2h((uint8_t*)final_states, (const uint8_t*)A.state, (size_t)n_games * 32);
+    sync();
+    diee_stats st[2];
+    memset(st, 0, sizeof st);
+    for (int s = 0; s < 2; ++s) {
+        read_counters(*this, (uint32_t)(1 + s), &st[s]);
+        st[s].seconds = secs; st[s].move_steps = searches[s];
+        st[s].plies = words[AW_TURNS0 + s]; st[s].fragments = words[AW_MOVES0 + s]; st[s].games = words[AW_RETIRED0 + s];
+        for (uint32_t b = 0; b < DIEE_BANDS; ++b) st[s].band_launches[b] = bands[s][b];
+    }
+    st[0].tail_iterations = B.tl_iterations; st[0].tail_launches = B.tl_with_rows; st[0].tail_spec_rows = B.tl_spec_rows;
+    if (stats) memcpy(stats, st, sizeof st);
+    if (res) {
+        res->wins_p1 = words[AW_WINS1]; res->wins_p2 = words[AW_WINS2]; res->draws = words[AW_DRAWS];
+        res->rounds = round; res->illegal_decodes = st[0].illegal_decodes + st[1].illegal_decodes; res->seconds = secs;
+    }
 }
 
 }  // namespace diee

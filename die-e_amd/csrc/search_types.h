@@ -216,4 +216,37 @@ struct PlayParams {
     uint32_t quirks;
 };
 
+// ---- the arena (diee_arena; versus.rs:160-318) ----------------------------------------------------------------------------------
+// Model-vs-model games of one call, all on the device: per round k_arena_split partitions the live games by side to move (stable,
+// ascending game index), each side's list is searched in the call's slot space (k_arena_gather -> mcts_run) and its moves are
+// played (k_arena_move) before the other side searches: both sides' trees share the slots, and a game is in one list only.
+enum ArenaWord {            // Arena::words
+    AW_COUNT0 = 0,          // games in player 1's list this round, [1] player 2's, [2] games alive (k_arena_split; what the host reads)
+    AW_LIVE = 2,
+    AW_WINS1 = 3, AW_WINS2, AW_DRAWS,
+    AW_TURNS0 = 6,          // turns player 1 took (skipped ones included), [7] player 2
+    AW_MOVES0 = 8,          // ... of which a move was applied, [9] player 2
+    AW_RETIRED0 = 10,       // games retired by a move of player 1, [11] player 2
+    AW_COUNT = 12
+};
+struct Arena {
+    BgState* state;         // [games]
+    BgState* initial;       // [games] the states the games started from
+    uint8_t* alive;         // [games]
+    int8_t* winner;         // [games] -1 player 1, +1 player 2, 0 none
+    uint32_t* retired_round;// [games] round in which the game was retired (0xFFFFFFFF: still alive)
+    int8_t* retired_side;   // [games] list it moved in when it was retired (-1: still alive)
+    uint32_t* live;         // [games] live list, ascending game index
+    uint32_t* list;         // [2][games] this round's lists of the two sides
+    uint32_t* words;        // [AW_COUNT]
+    uint32_t n_games;
+};
+struct ArenaParams {
+    unsigned long long seed;
+    uint32_t round, round_limit;
+    float inv_temperature;
+    uint32_t side;          // 0: player 1's list, 1: player 2's
+    uint32_t agent;         // DIEE_AGENT_RANDOM / DIEE_AGENT_MODEL of that player
+};
+
 }  // namespace diee

@@ -4,7 +4,8 @@ src/versus.rs: play() (:160-268), get_actions_for_player (:270-318), Game JSON s
 rollouts) is not provided: its rollout is broken in the reference (node.rs:181).
 
 `play` is written against a small backend interface so that the same driver can run on the engine or,
-in the parity tests, on the CPU oracle.
+in the parity tests, on the CPU oracle.  `play_device` is the same arena as ONE engine call (diee_arena): every round
+on the device, the same games bit for bit (Model and Random agents); DIEE_ARENA=device makes the callers use it.
 """
 import json
 import os
@@ -214,9 +215,10 @@ def get_actions_for_player(player, states, ids, rnd, mcts_config, temp, seed, ru
 
 
 def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, rules=None,
-         search1=None, search2=None):
+         search1=None, search2=None, max_rounds=0):
     """play(), versus.rs:160-268.  player1 plays side -1 in every game; the second half of the games starts
-    with side +1 to move (:172-174)."""
+    with side +1 to move (:172-174).  max_rounds > 0 stops the loop after that many rounds (the games still alive
+    are not in `games`); 0 plays to the end."""
     if rules is None:
         eng = player1.model or player2.model
         if eng is None:
@@ -238,7 +240,7 @@ def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, ro
     wins_p1 = wins_p2 = 0
     played = []
     round_count = 0
-    while alive.any():                         # :191
+    while alive.any() and (max_rounds == 0 or round_count < max_rounds):      # :191
         live = np.nonzero(alive)[0]
         p1 = live[states["player"][live] == -1]  # :195-196 partition by side to move
         p2 = live[states["player"][live] != -1]
@@ -280,6 +282,46 @@ def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, ro
     res = PlayResult(player1.player_type, player2.player_type, wins_p1, wins_p2, num_games, played)
     res.final_states = states
     res.rounds = round_count
+    return res
+
+
+def retired_order(winner, retired_round, retired_side):
+    """the order in which play() appends the games it retires: by round, within a round player 1's list before player 2's, within a
+    list by game index -> indices of the retired games (retired_round 0xFFFFFFFF = still alive: left out)"""
+    rr = np.asarray(retired_round, dtype=np.uint32)
+    done = np.nonzero(rr != 0xFFFFFFFF)[0]
+    side = np.asarray(retired_side)[done].astype(np.int64)
+    return done[np.lexsort((done, side, rr[done].astype(np.int64)))]
+
+
+def games_from_device(player1, player2, initial_states, winner, retired_round, retired_side):
+    """play()'s `games` from the per-game outputs of Engine.arena"""
+    names = {-1: player1.player_type, 1: player2.player_type, 0: Agent.NONE}
+    games = []
+    for g in retired_order(winner, retired_round, retired_side):
+        game = Game(player1.player_type, player2.player_type, initial_states[g], g)
+        game.winner = names[int(winner[g])]
+        games.append(game)
+    return games
+
+
+def play_device(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, max_rounds=0, engine=None):
+    """play() with every round on the device (Engine.arena, diee_arena): the same PlayResult -- wins, draws, rounds, final_states,
+    games in play()'s order -- from one engine call.  Model and Random agents; `engine` hosts a call whose players are both Random."""
+    from . import AGENT_MODEL, AGENT_RANDOM, arena
+    kinds = {Agent.MODEL: AGENT_MODEL, Agent.RANDOM: AGENT_RANDOM}
+    for p in (player1, player2):
+        if p.player_type not in kinds:
+            raise NotImplementedError("Agent::Mcts (vanilla MCTS with rollouts) is out of scope: SURVEY section 2 row 11")
+    e1, e2 = player1.model, player2.model
+    if e1 is None and e2 is None:
+        e1 = engine                            # two Random agents: any engine hosts the call
+    r = arena(e1, kinds[player1.player_type], e2, kinds[player2.player_type], num_games, mcts_config, temp, seed, round_limit, max_rounds)
+    games = games_from_device(player1, player2, r["initial_states"], r["winner"], r["retired_round"], r["retired_side"])
+    res = PlayResult(player1.player_type, player2.player_type, r["wins_p1"], r["wins_p2"], num_games, games)
+    res.final_states = r["final_states"]
+    res.rounds = r["rounds"]
+    res.device = r                             # the call's per-game outputs and per-player stats
     return res
 
 

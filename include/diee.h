@@ -284,6 +284,50 @@ diee_status diee_self_play_refill(diee_ctx*, const diee_batch* batches, uint32_t
                                   const diee_mcts_cfg* cfg, float temperature, uint32_t flags, uint32_t max_steps,
                                   diee_fragments* outs, diee_stats* stats);
 
+/* ---- the arena: play() / get_actions_for_player, src/versus.rs:160-318 -- n_games games between two agents in ONE call, every round on
+ * the device (the searches are diee_mcts_batch's; the moves are sampled, decoded, applied and judged where the trees are).
+ *   Game i starts from Backgammon::new, side -1 ("player 1") to move for i < n_games / 2, side +1 for the rest (:172-174); opening dice from
+ *   (seed, i, 0, TAG_INIT_ROLL).  Each round the live games are split by side to move, in ascending game index; player 1 searches its list with
+ *   step = 2 * round, game_ids = i, rounds = round, player 2 with step = 2 * round + 1 (what diee_mcts_batch is given by a host-side driver).
+ *   DIEE_AGENT_MODEL: child visits / their sum, ^(1 / temperature) (the engine's deterministic powf), the uniform of (seed, i, round, TAG_SAMPLE)
+ *   times the f64 total, first index whose running f64 sum exceeds it (:281-299).  DIEE_AGENT_RANDOM: plays[min(int(u * count), count - 1)] of
+ *   diee_bg_legal_moves' order with the same uniform (:308-317).  A root without children, an all-zero row or no legal play skips the turn
+ *   (skip_turn with the dice of (seed, i, round, TAG_MOVE_ROLL)) and that game is checked neither for a winner nor for the round limit in that
+ *   round (:225-228); otherwise decode, apply_move with those dice, check_winner, and with no winner and round + 1 >= round_limit the game is
+ *   retired as a draw (:233-237).  Agent::Mcts is not provided.
+ * The call runs on p1's stream, slots and tree arena with p1's search options (free_eval, spec_eval, shared_gpu, ...); for player 2's searches
+ * it borrows p2's network -- weights, activations, dispatch tables -- and touches nothing else of p2.  p2 on another device: DIEE_ERR_ARG;
+ * p2 == p1 is allowed; the ctx of a Random agent may be NULL as long as the other one is not (then that one hosts the call).  A Model agent
+ * whose ctx is NULL: DIEE_ERR_ARG, without loaded weights: DIEE_ERR_NO_WEIGHTS; a tic-tac-toe ctx: DIEE_ERR_UNSUPPORTED; n_games == 0 or
+ * round_limit == 0: DIEE_ERR_ARG.  flags: DIEE_FLAG_REF_QUIRKS (what a driver over diee_mcts_batch searches with), DIEE_FLAG_INVARIANT_NN.
+ * max_rounds = 0 plays to the end; otherwise the call stops after that many rounds and the live games keep winner 0, retired_round UINT32_MAX
+ * (retired_side -1).  The host synchronises with the device once per round (three words: the two sides' counts and the games alive) on top
+ * of what the searches do.
+ * stats[2], per player: the search counters of that player's searches (expansions, selections, nn_evals, ...); seconds = the call's wall clock;
+ * move_steps = its searches; plies = the turns it took, skipped ones included; fragments = the turns in which a move was applied (plies -
+ * fragments = skipped turns); games = games retired by one of its moves; band_launches[b] = its turns whose list had a size in band b
+ * (DIEE_BANDS).  The tail_* totals of the call are reported with player 1. */
+#define DIEE_AGENT_RANDOM 0   /* Agent::Random, versus.rs:308-317 */
+#define DIEE_AGENT_MODEL  1   /* Agent::Model,  versus.rs:279-306 */
+
+typedef struct {
+    uint32_t wins_p1, wins_p2, draws;   /* PlayResult, versus.rs:129-152 */
+    uint32_t rounds;                    /* round_count when the call ended */
+    uint64_t illegal_decodes;           /* versus.rs:229 would have panicked */
+    double   seconds;
+} diee_arena_result;
+
+diee_status diee_arena(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2,
+                       uint32_t n_games, const diee_mcts_cfg* cfg, float temperature,
+                       uint64_t seed, uint32_t round_limit, uint32_t max_rounds, uint32_t flags,
+                       diee_arena_result* res,
+                       int8_t* winner         /* [n_games]: -1 p1, +1 p2, 0 none; or NULL */,
+                       uint32_t* retired_round /* [n_games] or NULL */,
+                       int8_t* retired_side    /* [n_games]: 0 = moved in p1's list, 1 = p2's; or NULL */,
+                       diee_bg_state* initial_states /* [n_games] or NULL */,
+                       diee_bg_state* final_states   /* [n_games] or NULL */,
+                       diee_stats* stats /* [2], per player, or NULL */);
+
 /* ---- training-step kernels (no ctx: plain device pointers of the caller's framework, launched on `stream`, a
  * hipStream_t; NULL = the default stream).  AlphaZero::train (alphazero.rs:202-261) is tch autograd in the reference;
  * here the 38 tower convolutions of the step run on the engine's MFMA conv kernel in the NHWC token layout

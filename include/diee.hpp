@@ -9,6 +9,7 @@
 //   alpha_mcts_parallel + get_prob_tensor_parallel (src/mcts/alpha_mcts.rs:91, utils.rs:42) -> Engine::alpha_mcts_parallel
 //   AlphaZero::self_play_parallel (src/alphazero/alpha_parallel.rs:101-231)                -> Engine::self_play_parallel
 //   the self_play_iterations loop of learn_parallel (alpha_parallel.rs:49-62)              -> Engine::self_play_iterations
+//   play (src/versus.rs:160-268)                                                           -> Engine::arena
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -135,6 +136,27 @@ public:
         for (auto& f : fr) out.push_back(take(f));
         if (stats) *stats = st;
         return out;
+    }
+
+    // play() of versus.rs:160-268 in one engine call (diee_arena): this engine is player 1 (side -1 in every game) and hosts the call,
+    // `player2` lends its network.  A null player2 with agent2 = DIEE_AGENT_RANDOM is a random opponent.
+    struct ArenaResult {
+        diee_arena_result result;
+        std::vector<int8_t> winner, retired_side;                // per game: -1 player 1, +1 player 2, 0 none; the list it moved in when retired
+        std::vector<uint32_t> retired_round;                     // UINT32_MAX: still alive (max_rounds)
+        std::vector<Backgammon> initial_states, final_states;
+        diee_stats stats[2];
+    };
+    ArenaResult arena(Engine* player2, const MctsConfig& cfg, float temperature, uint64_t seed, uint32_t num_games = 400, uint32_t round_limit = 400,
+                      int agent1 = DIEE_AGENT_MODEL, int agent2 = DIEE_AGENT_MODEL, uint32_t max_rounds = 0, bool ref_quirks = true) {
+        ArenaResult r;
+        r.winner.resize(num_games); r.retired_side.resize(num_games); r.retired_round.resize(num_games);
+        r.initial_states.resize(num_games); r.final_states.resize(num_games);
+        chk(diee_arena(ctx_, agent1, player2 ? player2->ctx_ : nullptr, agent2, num_games, &cfg, temperature, seed, round_limit, max_rounds,
+                       ref_quirks ? DIEE_FLAG_REF_QUIRKS : 0u, &r.result, r.winner.data(), r.retired_round.data(), r.retired_side.data(),
+                       r.initial_states.data(), r.final_states.data(), r.stats));
+        if (r.result.illegal_decodes) throw Error(DIEE_ERR_CAPACITY, "decoded action is not a valid move (versus.rs:229)");
+        return r;
     }
 
     diee_ctx* raw() { return ctx_; }
