@@ -11,6 +11,7 @@ reference's tests:
                                                   -> Engine.alpha_mcts_parallel
     AlphaZero::self_play_parallel (src/alphazero/alpha_parallel.rs:101) -> Engine.self_play_parallel
     play (src/versus.rs:160-268)                  -> arena / Engine.arena (die-e_amd/versus.py: play_device)
+    mct_search (src/mcts/simple_mcts.rs:10-39)    -> Engine.mct_search (Agent::Mcts)
 
 There is no CPU fallback: the library must load and a GPU must be present, otherwise the
 constructor raises.  Import with importlib.import_module("die-e_amd") (the directory name is
@@ -30,7 +31,7 @@ NO_MOVE = -2
 GAME_TTT, GAME_BACKGAMMON = 0, 1
 FLAG_REF_QUIRKS = 1
 FLAG_INVARIANT_NN = 2
-AGENT_RANDOM, AGENT_MODEL = 0, 1                         # DIEE_AGENT_*: the agents of Engine.arena
+AGENT_RANDOM, AGENT_MODEL, AGENT_MCTS = 0, 1, 2          # DIEE_AGENT_*: the agents of Engine.arena
 BAND_BOUNDS = (16, 32, 64, 128, 256, 512, 928, 1024)     # DIEE_BANDS: upper bounds of Stats.band_* (the ninth band is everything above)
 
 OK, ERR_ARG, ERR_HIP, ERR_NO_WEIGHTS, ERR_CAPACITY, ERR_UNSUPPORTED = range(6)
@@ -47,7 +48,7 @@ assert TTT_STATE.itemsize == 32
 # of include/diee_dev.h are listed in DEV_EXPORTS
 EXPORTS = [
     "diee_create", "diee_destroy", "diee_last_error", "diee_version", "diee_set_option", "diee_get_option", "diee_device_pci_bus_id", "diee_weights_count",
-    "diee_random_weights", "diee_load_weights", "diee_nn_forward", "diee_mcts_batch", "diee_self_play",
+    "diee_random_weights", "diee_load_weights", "diee_nn_forward", "diee_mcts_batch", "diee_mcts_vanilla_batch", "diee_self_play",
     "diee_self_play_multi", "diee_self_play_refill", "diee_arena", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
     "diee_train_conv3x3", "diee_train_im2col3x3",
     "diee_train_scratch_floats", "diee_train_bn_relu_fwd", "diee_train_bn_relu_bwd", "diee_train_colsum",
@@ -108,6 +109,15 @@ class ArenaResult(C.Structure):
                 ("illegal_decodes", C.c_uint64), ("seconds", C.c_double)]
 
 
+class VanillaStats(C.Structure):
+    """diee_vanilla_stats"""
+    _fields_ = ([(n, C.c_uint64) for n in ("iterations", "expansions", "terminal_hits", "dead_end_hits", "rollouts", "rollout_plies",
+                                           "rollout_decided", "depth_sum")] + [("seconds", C.c_double)])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DevLaunch(C.Structure):
     """diee_dev_launch (include/diee_dev.h)"""
     _fields_ = [("family", C.c_int), ("geometry", C.c_int), ("boards", C.c_int), ("kernel", C.c_char * 120)]
@@ -157,6 +167,8 @@ def load_library(path=None):
     L.diee_nn_forward.argtypes = [vp, vp, u32, vp, vp]; L.diee_nn_forward.restype = C.c_int
     L.diee_mcts_batch.argtypes = [vp, vp, u32, vp, u64, u32, vp, vp, u32, vp, vp, vp, vp]
     L.diee_mcts_batch.restype = C.c_int
+    L.diee_mcts_vanilla_batch.argtypes = [vp, vp, u32, vp, u64, vp, vp, u32, vp, vp, vp, vp, u32, vp]
+    L.diee_mcts_vanilla_batch.restype = C.c_int
     L.diee_self_play.argtypes = [vp, u32, u32, vp, f32, u64, u32, u32, vp, vp]; L.diee_self_play.restype = C.c_int
     L.diee_self_play_multi.argtypes = [vp, vp, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_multi.restype = C.c_int
     L.diee_self_play_refill.argtypes = [vp, vp, u32, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_refill.restype = C.c_int
@@ -415,6 +427,23 @@ class Engine:
                                           probs.ctypes.data, nch.ctypes.data, rv.ctypes.data, C.byref(st)))
         return {"probs": probs, "n_children": nch, "root_visits": rv, "stats": st.as_dict()}
 
+    def mct_search(self, states, cfg, seed=0, game_ids=None, rounds=None, ref_quirks=True, cap=256):
+        """mct_search (simple_mcts.rs:10-39) per root, Agent::Mcts: vanilla UCB1 search with random rollouts (diee_mcts_vanilla_batch; no
+        weights needed).  ref_quirks: the reference's rollout, which plays nothing (Q22) -> dict(plays int8 [n,4] (all NO_MOVE =
+        EMPTY_MOVE), n_children, child_visits / child_values [n,cap] in creation order, stats)"""
+        s = _states(states); n = len(s)
+        plays = np.full((n, 4), NO_MOVE, dtype=np.int8)
+        nch = np.zeros(n, dtype=np.uint32)
+        cv = np.zeros((n, cap), dtype=np.float32); cw = np.zeros((n, cap), dtype=np.float32)
+        gi = None if game_ids is None else np.ascontiguousarray(game_ids, dtype=np.uint32)
+        rd = None if rounds is None else np.ascontiguousarray(rounds, dtype=np.uint32)
+        st = VanillaStats()
+        self._chk(self._L.diee_mcts_vanilla_batch(self._h, s.ctypes.data, n, C.byref(cfg), seed,
+                                                  None if gi is None else gi.ctypes.data, None if rd is None else rd.ctypes.data,
+                                                  FLAG_REF_QUIRKS if ref_quirks else 0, plays.ctypes.data, nch.ctypes.data,
+                                                  cv.ctypes.data, cw.ctypes.data, cap, C.byref(st)))
+        return {"plays": plays, "n_children": nch, "child_visits": cv, "child_values": cw, "stats": st.as_dict()}
+
     def _take_fragments(self, fr, out, copy=True):
         """diee_fragments -> numpy.  copy=True: arrays of their own, the engine's blocks go back at once.  copy=False: views of
         the engine-owned (page-locked) arrays, valid until out["free"]() -- what a host that binds the C ABI works with."""
@@ -497,7 +526,7 @@ def arena(engine1, agent1, engine2, agent2, n_games, cfg, temperature=1.25, seed
           ref_quirks=True, invariant_nn=False):
     """play() of versus.rs:160-268 in one engine call (diee_arena).  engine1 is player 1 (side -1 in every game) and hosts the call,
     engine2 (an Engine on the same device, engine1 again, or None for a Random agent) lends player 2's network; engine1 may be None
-    for a Random agent, then engine2 hosts.  agent1 / agent2: AGENT_MODEL | AGENT_RANDOM.  -> dict(wins_p1, wins_p2, draws, rounds,
+    for a Random or Mcts agent, then engine2 hosts.  agent1 / agent2: AGENT_MODEL | AGENT_RANDOM | AGENT_MCTS.  -> dict(wins_p1, wins_p2, draws, rounds,
     illegal_decodes, seconds, winner int8 [n], retired_round uint32 [n] (0xFFFFFFFF: still alive, max_rounds), retired_side int8 [n],
     initial_states, final_states, stats [per player]); raises if a sampled action did not decode to a valid move (versus.rs:229
     panics)"""

@@ -89,7 +89,7 @@ __global__ void k_arena_gather(Arena A, Slots S, Segs G, uint32_t side, uint32_t
 
 // get_actions_for_player (versus.rs:270-318) and the body of play()'s per-game loop (:220-266) for one game of the side that just
 // searched (Model) or is about to pick (Random), by one wave
-__global__ __launch_bounds__(64) void k_arena_move(Tree T, Arena A, uint32_t n, ArenaParams P, uint32_t* overflow) {
+__global__ __launch_bounds__(64) void k_arena_move(Tree T, Arena A, uint32_t n, ArenaParams P, uint32_t* overflow, const uint32_t* mcts_play) {
     __shared__ float row[1352];
     __shared__ WaveScratch sc;
     const uint32_t slot = blockIdx.x;
@@ -98,7 +98,9 @@ __global__ __launch_bounds__(64) void k_arena_move(Tree T, Arena A, uint32_t n, 
     const uint32_t g = A.list[(size_t)P.side * A.n_games + slot];
     BgState s = load_state(&A.state[g]);
     uint32_t play = pack_play(kNoMove, kNoMove, kNoMove, kNoMove);      // EMPTY_MOVE
-    if (P.agent != 0u) {                                        // Agent::Model, :279-306
+    if (P.agent == 2u) {                                        // Agent::Mcts, :303-306: mct_search's answer (vanilla_kernels.hip)
+        play = mcts_play[slot];
+    } else if (P.agent != 0u) {                                 // Agent::Model, :279-306
         const size_t base = (size_t)slot * T.node_cap;
         const uint32_t k = meta_nch(T.meta[base]), fc = T.first_child[base];
         if (k != 0) {                                           // :292 root.children.is_empty() -> EMPTY_MOVE
@@ -149,9 +151,10 @@ void launch_arena_gather(hipStream_t st, const Arena& A, const Slots& S, const S
     if (!n) return;
     hipLaunchKernelGGL(k_arena_gather, dim3((n + 255) / 256), dim3(256), 0, st, A, S, G, side, n, round);
 }
-void launch_arena_move(hipStream_t st, const Tree& T, const Arena& A, uint32_t n, const ArenaParams& P, uint32_t* overflow) {
+void launch_arena_move(hipStream_t st, const Tree& T, const Arena& A, uint32_t n, const ArenaParams& P, uint32_t* overflow,
+                       const uint32_t* mcts_play) {
     if (!n) return;
-    hipLaunchKernelGGL(k_arena_move, dim3(n), dim3(64), 0, st, T, A, n, P, overflow);
+    hipLaunchKernelGGL(k_arena_move, dim3(n), dim3(64), 0, st, T, A, n, P, overflow, mcts_play);
 }
 
 }  // namespace diee

@@ -453,7 +453,8 @@ __host__ __device__ inline void philox4x32(uint32_t k0, uint32_t k1, uint32_t c0
     o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
 }
 constexpr uint32_t kTagInitRoll = 0xFFFFFFFFu, kTagMoveRoll = 0xFFFFFFFEu, kTagSample = 0xFFFFFFFDu,
-                   kTagDirichlet = 0xFFFFFFFCu;
+                   kTagDirichlet = 0xFFFFFFFCu,
+                   kTagVanilla = 0xFFFFFFFBu;       // Agent::Mcts: ord = iteration << 12 | k (k = 0: the new child's dice, 1 + p: rollout ply p)
 // roll_die, backgammon_logic.rs:100-104: two iid uniform 1..=6
 __host__ __device__ inline void draw_dice(uint64_t seed, uint32_t game, uint32_t round, uint32_t tag,
                                           uint32_t ord, int& d0, int& d1) {

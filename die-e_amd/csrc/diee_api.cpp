@@ -235,6 +235,16 @@ diee_status diee_mcts_batch(diee_ctx* c, const diee_bg_state* roots, uint32_t n,
     API_END(c)
 }
 
+diee_status diee_mcts_vanilla_batch(diee_ctx* c, const diee_bg_state* roots, uint32_t n, const diee_mcts_cfg* cfg, uint64_t seed,
+                                    const uint32_t* game_ids, const uint32_t* rounds, uint32_t flags, int8_t* plays, uint32_t* n_children,
+                                    float* child_visits, float* child_values, uint32_t cap, diee_vanilla_stats* stats) {
+    API_BEGIN(c)
+    Engine* e = bg(c);                                          // (a tic-tac-toe ctx: DIEE_ERR_UNSUPPORTED)
+    if (!roots || !cfg || !plays) throw EngineError(DIEE_ERR_ARG, "null pointer");
+    e->mcts_vanilla_batch(roots, n, cfg, seed, game_ids, rounds, flags, plays, n_children, child_visits, child_values, cap, stats);
+    API_END(c)
+}
+
 diee_status diee_self_play(diee_ctx* c, uint32_t n_games, uint32_t first_game_id, const diee_mcts_cfg* cfg,
                            float temperature, uint64_t seed, uint32_t flags, uint32_t max_steps,
                            diee_fragments* out, diee_stats* stats) {

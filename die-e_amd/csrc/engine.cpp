@@ -15,6 +15,7 @@ void cluster_baton_register(int device, int delta);
 void nn_reset_cluster(Engine& e);
 void nn_disable_cluster(Engine& e);
 void free_search(SearchBufs*);
+void free_vanilla(VanillaBufs*);
 void pinned_pool_set_cap_mb(size_t mb);
 size_t pinned_pool_cap_mb();
 
@@ -39,6 +40,7 @@ const OptEntry kOptions[] = {
     {"free_rollout_steps", nullptr, &Options::free_rollout_steps, nullptr}, {"free_cand_max", nullptr, &Options::free_cand_max, nullptr},
     {"free_ring", nullptr, &Options::free_ring, nullptr}, {"free_iter_cap", nullptr, &Options::free_iter_cap, nullptr}, {"free_cand_x4", nullptr, &Options::free_cand_x4, nullptr},
     {"free_lag_boost", nullptr, &Options::free_lag_boost, nullptr}, {"free_lag_step", nullptr, &Options::free_lag_step, nullptr}, {"free_lds_nodes", nullptr, &Options::free_lds_nodes, nullptr},
+    {"vanilla_iters_per_launch", nullptr, &Options::vanilla_iters_per_launch, nullptr},
     {"path_cap", nullptr, &Options::path_cap, nullptr}, {"nodes_per_expansion", nullptr, &Options::nodes_per_expansion, nullptr},
     {"deliver_stage_rows", nullptr, &Options::deliver_stage_rows, nullptr}, {"deliver_rows_per_game", nullptr, &Options::deliver_rows_per_game, nullptr},
     {"trace_steps", &Options::trace_steps, nullptr, nullptr}, {"trace_dispatch", &Options::trace_dispatch, nullptr, nullptr},
@@ -126,6 +128,7 @@ Engine::~Engine() {
     if (stream) cluster_baton_register(device, -1);
     free_net(net);
     free_search(search);
+    free_vanilla(vanilla);
     if (stream) (void)hipStreamDestroy(stream);
 }
 

@@ -43,6 +43,7 @@ struct DevBuf {
 
 struct NetWeights;   // nn_host.cpp
 struct SearchBufs;   // search_host.cpp
+struct VanillaBufs;  // vanilla_host.cpp
 
 // Per-ctx switches (diee_set_option, include/diee.h).  Defaults here; the environment (DIEE_<KEY IN CAPITALS>, e.g. DIEE_TOWER_CL for
 // "tower_cl") is read ONCE, when the ctx is created, as a development override of these defaults; nothing reads it afterwards.
@@ -81,6 +82,7 @@ struct Options {
     uint32_t spec_ring_mb = 8192;           // HBM the tail's ring of evaluated rows may take (MiB): (iterations + 1) launches x rows x 5.7 KB; a search whose ring
                                             // would be larger runs one launch per iteration instead (iterations = 1600 x 512 rows: 4.7 GB)
     uint32_t path_cap = 64, nodes_per_expansion = 128;
+    uint32_t vanilla_iters_per_launch = 0;  // Agent::Mcts: iterations a game runs per launch at most; 0: derived from round_limit (vanilla_host.cpp) -- same results
     // output delivery
     uint32_t deliver_stage_rows = 16384, deliver_rows_per_game = 128;
     // development traces on stderr
@@ -123,6 +125,10 @@ public:
     void arena(NetWeights* net1, int agent1, NetWeights* net2, int agent2, uint32_t n_games, const diee_mcts_cfg* cfg, float temperature,
                uint64_t seed, uint32_t round_limit, uint32_t max_rounds, uint32_t flags, diee_arena_result* res, int8_t* winner,
                uint32_t* retired_round, int8_t* retired_side, diee_bg_state* initial_states, diee_bg_state* final_states, diee_stats* stats);
+    // Agent::Mcts: mct_search (simple_mcts.rs:10-39) for n roots; needs no weights (vanilla_host.cpp)
+    void mcts_vanilla_batch(const diee_bg_state* roots, uint32_t n, const diee_mcts_cfg* cfg, uint64_t seed, const uint32_t* game_ids,
+                            const uint32_t* rounds, uint32_t flags, int8_t* plays, uint32_t* n_children, float* child_visits,
+                            float* child_values, uint32_t cap, diee_vanilla_stats* stats);
     uint32_t refill_areas = 0;       // record areas the last self_play_refill allocated (read-only option refill_record_areas)
 
     int device;
@@ -153,6 +159,7 @@ public:
     DevBuf<uint32_t> flags_dev;      // [0] capacity-overflow flag
     NetWeights* net = nullptr;
     SearchBufs* search = nullptr;
+    VanillaBufs* vanilla = nullptr;
 };
 
 }  // namespace diee

@@ -129,7 +129,17 @@ void launch_arena_split(hipStream_t st, const Arena& A, uint32_t n_live);
 // the n games of side `side`'s list -> slots 0 ... n - 1 (roots, game_id = game index, round), one batch spanning them
 void launch_arena_gather(hipStream_t st, const Arena& A, const Slots& S, const Segs& G, uint32_t side, uint32_t n, uint32_t round);
 // the moves of the n games of P.side's list: sampled from their searched roots (slot = position in the list) or picked among the legal plays
-void launch_arena_move(hipStream_t st, const Tree& T, const Arena& A, uint32_t n, const ArenaParams& P, uint32_t* overflow);
+// (mcts_play: the answers of the side's vanilla search, slot = position in the list -- read when P.agent is DIEE_AGENT_MCTS)
+void launch_arena_move(hipStream_t st, const Tree& T, const Arena& A, uint32_t n, const ArenaParams& P, uint32_t* overflow,
+                       const uint32_t* mcts_play = nullptr);
+// vanilla_kernels.hip (search_types.h, Vanilla): Agent::Mcts.  init: the roots' nodes; one launch_vanilla = at most V.budget iterations per
+// game; result: V.out_play, and where asked for the root's children (count; visits / values [n][cap] in creation order)
+void launch_vanilla_init(hipStream_t st, const Vanilla& V, uint32_t n);
+void launch_vanilla(hipStream_t st, const Vanilla& V, uint32_t n);
+void launch_vanilla_result(hipStream_t st, const Vanilla& V, uint32_t n, uint32_t* n_children, float* child_visits, float* child_values,
+                           uint32_t cap);
+void launch_vanilla_gather(hipStream_t st, const Arena& A, uint32_t side, uint32_t n, uint32_t round, BgState* roots, uint32_t* game_id,
+                           uint32_t* rounds);
 constexpr uint32_t kRootIteration = 0xFFFFFFFFu;
 constexpr uint32_t kNoNextIteration = 0xFFFFFFFEu;
 

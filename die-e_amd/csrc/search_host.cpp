@@ -17,6 +17,7 @@
 #include "engine.h"
 #include "launch.h"
 #include "nn_host.h"
+#include "vanilla_host.h"
 
 namespace diee {
 
@@ -910,10 +911,13 @@ void Engine::arena(NetWeights* net1, int agent1, NetWeights* net2, int agent2, u
     NetWeights* const nets[2] = {net1, net2};
     const int agents[2] = {agent1, agent2};
     for (int s = 0; s < 2; ++s) {
-        if (agents[s] != DIEE_AGENT_RANDOM && agents[s] != DIEE_AGENT_MODEL) throw EngineError(DIEE_ERR_ARG, "agent: DIEE_AGENT_RANDOM or DIEE_AGENT_MODEL");
+        if (agents[s] != DIEE_AGENT_RANDOM && agents[s] != DIEE_AGENT_MODEL && agents[s] != DIEE_AGENT_MCTS)
+            throw EngineError(DIEE_ERR_ARG, "agent: DIEE_AGENT_RANDOM, DIEE_AGENT_MODEL or DIEE_AGENT_MCTS");
         if (agents[s] == DIEE_AGENT_MODEL && (!nets[s] || !nets[s]->loaded)) throw EngineError(DIEE_ERR_NO_WEIGHTS, "diee_load_weights has not been called for a Model agent's ctx");
     }
-    reserve_search(*this, n_games, cfg->iterations);
+    const bool any_model = agent1 == DIEE_AGENT_MODEL || agent2 == DIEE_AGENT_MODEL, any_mcts = agent1 == DIEE_AGENT_MCTS || agent2 == DIEE_AGENT_MCTS;
+    if (any_mcts) vanilla_check_cfg(*cfg);
+    reserve_search(*this, n_games, any_mcts && !any_model ? 0u : cfg->iterations);      // (the Model searches' tree arena: a vanilla search has its own slabs)
     SearchBufs& B = *search;
     B.noise_rows = 0;
     // the two networks for the duration of the call: no sampled timing (as in mcts_batch), DIEE_FLAG_INVARIANT_NN, activations for n_games rows
@@ -943,6 +947,10 @@ void Engine::arena(NetWeights* net1, int agent1, NetWeights* net2, int agent2, u
     B.tl_iterations = B.tl_launched = B.tl_with_rows = B.tl_spec_rows = B.tl_syncs = 0;
     uint32_t tl_need[2] = {0, 0}, fr_need[2] = {0, 0};               // launches each side's previous search needed (size the first chunk of the next)
     HIPCHK(hipMemsetAsync(B.step_log.p, 0, sizeof(unsigned long long) * 2 * kStepLog, stream));
+    if (any_mcts) {                                                     // the slabs for the call's widest search; one counter block per player
+        (void)vanilla_reserve(*this, n_games, *cfg, seed, flags);
+        vanilla_zero_counters(*this);
+    }
     launch_arena_init(stream, A, seed);
     HIPCHK(hipGetLastError());
     sync();
@@ -982,8 +990,16 @@ void Engine::arena(NetWeights* net1, int agent1, NetWeights* net2, int agent2, u
                 HIPCHK(hipMemcpyAsync(acc((int)s), cnt0, sizeof(unsigned long long) * CNT_COUNT, hipMemcpyDeviceToDevice, stream));
                 ++searches[s];
             }
+            const uint32_t* mcts_play = nullptr;
+            if (agents[s] == DIEE_AGENT_MCTS) {                         // :303-306
+                const Vanilla V = vanilla_reserve(*this, cnt[s], *cfg, seed, flags, s);
+                launch_vanilla_gather(stream, A, s, cnt[s], round, V.roots, V.game_id, V.round);
+                vanilla_search(*this, V, cnt[s]);
+                mcts_play = V.out_play;
+                ++searches[s];
+            }
             const ArenaParams P{seed, round, round_limit, inv_t, s, (uint32_t)agents[s]};
-            launch_arena_move(stream, tree_view(B), A, cnt[s], P, flags_dev.p);      // :220-266
+            launch_arena_move(stream, tree_view(B), A, cnt[s], P, flags_dev.p, mcts_play);      // :220-266
         }
         HIPCHK(hipGetLastError());
         ++round;                                                        // :219
@@ -1005,6 +1021,11 @@ void Engine::arena(NetWeights* net1, int agent1, NetWeights* net2, int agent2, u
         st[s].seconds = secs; st[s].move_steps = searches[s];
         st[s].plies = words[AW_TURNS0 + s]; st[s].fragments = words[AW_MOVES0 + s]; st[s].games = words[AW_RETIRED0 + s];
         for (uint32_t b = 0; b < DIEE_BANDS; ++b) st[s].band_launches[b] = bands[s][b];
+        if (agents[s] == DIEE_AGENT_MCTS) {                             // the fields that have a meaning for a vanilla search
+            diee_vanilla_stats vs;
+            vanilla_read_counters(*this, (uint32_t)s, &vs);
+            st[s].selections = vs.iterations; st[s].expansions = vs.expansions; st[s].terminal_hits = vs.terminal_hits; st[s].depth_sum = vs.depth_sum;
+        }
     }
     st[0].tail_iterations = B.tl_iterations; st[0].tail_launches = B.tl_with_rows; st[0].tail_spec_rows = B.tl_spec_rows;
     if (stats) memcpy(stats, st, sizeof st);

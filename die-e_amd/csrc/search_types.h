@@ -246,7 +246,39 @@ struct ArenaParams {
     uint32_t round, round_limit;
     float inv_temperature;
     uint32_t side;          // 0: player 1's list, 1: player 2's
-    uint32_t agent;         // DIEE_AGENT_RANDOM / DIEE_AGENT_MODEL of that player
+    uint32_t agent;         // DIEE_AGENT_RANDOM / DIEE_AGENT_MODEL / DIEE_AGENT_MCTS of that player
+};
+
+// ---- Agent::Mcts (diee_mcts_vanilla_batch; simple_mcts.rs:10-39, node.rs) ---------------------------------------------------------
+// Vanilla UCB1 search with random rollouts, one wavefront per game (vanilla_kernels.hip).  A game's tree is a slab of node_cap =
+// iterations + 1 nodes in HBM (an iteration creates at most one node) that persists from launch to launch: a launch runs at most
+// `budget` iterations per game, the host launches ceil(iterations / budget) times, and since an iteration reads nothing but the slab
+// and the game's own words the result does not depend on the budget.  A node's children are created iterations apart, so they are not
+// contiguous: they hang on a list (head = the newest, `next` = the sibling created before it); creation order = ascending node index.
+enum VanillaCounter { VC_ITERATIONS = 0, VC_EXPANSIONS, VC_TERMINAL, VC_DEAD_END, VC_ROLLOUTS, VC_PLIES, VC_DECIDED, VC_DEPTH_SUM, VC_COUNT };
+constexpr uint32_t kVanillaUnknown = 0xFFFFFFFFu;   // Vanilla::nplays of a node whose plays have not been enumerated yet; the end of a list
+struct Vanilla {
+    BgState* state;         // [slots][node_cap] Node.state (dice frozen at creation)
+    uint32_t* parent;       // [slots][node_cap] local index (the root: kVanillaUnknown)
+    uint32_t* nplays;       // [slots][node_cap] legal plays of the node's state = Node.expandable_moves.len() + children.len()
+    uint32_t* ncreated;     // [slots][node_cap] children created so far
+    uint32_t* visits;       // [slots][node_cap] Node.visits (integers; the reference's f32 counts them exactly)
+    float* value;           // [slots][node_cap] Node.value
+    uint32_t* play;         // [slots][node_cap] the play that led here (bytes f1, t1, f2, t2)
+    uint32_t* head;         // [slots][node_cap] the child created last (kVanillaUnknown: none)
+    uint32_t* next;         // [slots][node_cap] the sibling created before this node
+    uint32_t* done;         // [slots] iterations the game has run; kVanillaUnknown: it runs none (finished root, root without a play, capacity)
+    uint32_t* used;         // [slots] nodes of the slab in use
+    BgState* roots;         // [slots] (the caller fills the roots and their RNG keys)
+    uint32_t* game_id;      // [slots] RNG key
+    uint32_t* round;        // [slots] RNG key
+    const float* ln;        // [iterations + 2] ln[k] = (float)log((double)k), built by the host (ln[0] is never read)
+    unsigned long long* counters;   // [slots][VC_COUNT] running totals of the slot (the host sums them)
+    uint32_t* out_play;     // [slots] the answer: the root's most visited child's play, or EMPTY_MOVE
+    uint32_t* overflow;     // capacity flag (bit0: more than kMaxPlays legal plays / the sequence table)
+    unsigned long long seed;
+    uint32_t node_cap, iterations, round_limit, budget, quirks;
+    float c;
 };
 
 }  // namespace diee

@@ -1,15 +1,17 @@
 """Arena: the second caller of the hot path.  Mirrors the reference's
 src/versus.rs: play() (:160-268), get_actions_for_player (:270-318), Game JSON save / load / replay
-(:27-122).  Model agents search on the HIP engine (diee_mcts_batch); the Mcts agent (vanilla UCB1 with
-rollouts) is not provided: its rollout is broken in the reference (node.rs:181).
+(:27-122).  Model agents search on the HIP engine (diee_mcts_batch), and so does the Mcts agent (vanilla UCB1 with
+rollouts, diee_mcts_vanilla_batch): by default the reference's agent as written, whose rollout plays nothing (node.rs:181,
+Q22); DIEE_VANILLA_ROLLOUTS=1 (or vanilla_rollouts=True) turns the quirk off -- opt-in and logged, like the project's other deviations.
 
 `play` is written against a small backend interface so that the same driver can run on the engine or,
 in the parity tests, on the CPU oracle.  `play_device` is the same arena as ONE engine call (diee_arena): every round
-on the device, the same games bit for bit (Model and Random agents); DIEE_ARENA=device makes the callers use it.
+on the device, the same games bit for bit (Model, Mcts and Random agents); DIEE_ARENA=device makes the callers use it.
 """
 import json
 import os
 import secrets
+import sys
 
 import numpy as np
 
@@ -66,6 +68,19 @@ class EngineSearch:
     def mcts(self, states, cfg, seed, step, ids, rounds):
         r = self.e.alpha_mcts_parallel(states, cfg, seed, step, ids, rounds, ref_quirks=True)
         return r["probs"], r["n_children"]
+
+    def vanilla(self, states, cfg, seed, ids, rounds, ref_quirks):
+        """mct_search per game (Agent::Mcts) -> plays int8 [n,4]; needs no weights"""
+        return self.e.mct_search(states, cfg, seed, ids, rounds, ref_quirks=ref_quirks)["plays"]
+
+
+def vanilla_rollouts_from_env(log=None):
+    """DIEE_VANILLA_ROLLOUTS=1: the Mcts agent's rollouts are played (the reference's Q22 off), opt-in and logged"""
+    on = os.environ.get("DIEE_VANILLA_ROLLOUTS") == "1"
+    if on:
+        (log or (lambda m: sys.stderr.write(m + "\n")))("[diee] DIEE_VANILLA_ROLLOUTS=1: Agent::Mcts plays its rollouts "
+                                                        "(deviation from the reference, whose simulate() returns 0: Q22)")
+    return on
 
 
 def new_states(n):
@@ -183,7 +198,7 @@ class PlayResult:                              # versus.rs:129-152
                 f"Winrate: {self.winrate * 100.}%\n")
 
 
-def get_actions_for_player(player, states, ids, rnd, mcts_config, temp, seed, rules, search, side):
+def get_actions_for_player(player, states, ids, rnd, mcts_config, temp, seed, rules, search, side, vanilla_quirks=True):
     """versus.rs:270-318 -> plays int8 [n,4] (all NO_MOVE = EMPTY_MOVE)"""
     n = len(states)
     plays = np.full((n, 4), NO_MOVE, dtype=np.int8)
@@ -211,14 +226,22 @@ def get_actions_for_player(player, states, ids, rnd, mcts_config, temp, seed, ru
             if cnt[i]:
                 plays[i] = vm[i][min(int(uni[i] * cnt[i]), cnt[i] - 1)]
         return plays
-    raise NotImplementedError("Agent::Mcts (vanilla MCTS with rollouts) is out of scope: SURVEY section 2 row 11")
+    if search is None:
+        raise NotImplementedError("Agent::Mcts (vanilla MCTS with rollouts) runs on the engine: give the player an engine (Player.model) "
+                                  "or pass a search object with .vanilla()")
+    # :303-306 mct_search per game (the drawn uniform is not used)
+    return np.asarray(search.vanilla(states, mcts_config, seed, ids.astype(np.uint32), np.full(n, rnd, dtype=np.uint32), vanilla_quirks),
+                      dtype=np.int8).reshape(n, 4)
 
 
 def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, rules=None,
-         search1=None, search2=None, max_rounds=0):
+         search1=None, search2=None, max_rounds=0, vanilla_rollouts=None):
     """play(), versus.rs:160-268.  player1 plays side -1 in every game; the second half of the games starts
     with side +1 to move (:172-174).  max_rounds > 0 stops the loop after that many rounds (the games still alive
-    are not in `games`); 0 plays to the end."""
+    are not in `games`); 0 plays to the end.  An Mcts player searches on its engine (Player.model) or on search1 / search2;
+    vanilla_rollouts: its rollouts are played (Q22 off); None reads DIEE_VANILLA_ROLLOUTS."""
+    if vanilla_rollouts is None:
+        vanilla_rollouts = Agent.MCTS in (player1.player_type, player2.player_type) and vanilla_rollouts_from_env()
     if rules is None:
         eng = player1.model or player2.model
         if eng is None:
@@ -227,6 +250,10 @@ def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, ro
     if search1 is None and player1.player_type == Agent.MODEL:
         search1 = EngineSearch(player1.model)
     if search2 is None and player2.player_type == Agent.MODEL:
+        search2 = EngineSearch(player2.model)
+    if search1 is None and player1.player_type == Agent.MCTS and player1.model is not None:
+        search1 = EngineSearch(player1.model)
+    if search2 is None and player2.player_type == Agent.MCTS and player2.model is not None:
         search2 = EngineSearch(player2.model)
 
     states = new_states(num_games)
@@ -246,7 +273,8 @@ def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, ro
         p2 = live[states["player"][live] != -1]
         acts = {}
         for side, (pl, ids, srch) in enumerate(((player1, p1, search1), (player2, p2, search2))):
-            a = get_actions_for_player(pl, states[ids], ids, round_count, mcts_config, temp, seed, rules, srch, side)
+            a = get_actions_for_player(pl, states[ids], ids, round_count, mcts_config, temp, seed, rules, srch, side,
+                                       vanilla_quirks=not vanilla_rollouts)
             for k, g in enumerate(ids):
                 acts[int(g)] = a[k]
         rnd = round_count
@@ -305,18 +333,24 @@ def games_from_device(player1, player2, initial_states, winner, retired_round, r
     return games
 
 
-def play_device(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, max_rounds=0, engine=None):
+def play_device(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, max_rounds=0, engine=None,
+                vanilla_rollouts=None):
     """play() with every round on the device (Engine.arena, diee_arena): the same PlayResult -- wins, draws, rounds, final_states,
-    games in play()'s order -- from one engine call.  Model and Random agents; `engine` hosts a call whose players are both Random."""
-    from . import AGENT_MODEL, AGENT_RANDOM, arena
-    kinds = {Agent.MODEL: AGENT_MODEL, Agent.RANDOM: AGENT_RANDOM}
-    for p in (player1, player2):
-        if p.player_type not in kinds:
-            raise NotImplementedError("Agent::Mcts (vanilla MCTS with rollouts) is out of scope: SURVEY section 2 row 11")
+    games in play()'s order -- from one engine call.  Model, Mcts and Random agents; `engine` hosts a call none of whose players brings an
+    engine.  vanilla_rollouts as in play(): ONE flag word governs both players' searches of a diee_arena call, so an Mcts agent with played
+    rollouts against a Model agent (which play() searches with the quirks on) is the host driver's to run."""
+    from . import AGENT_MCTS, AGENT_MODEL, AGENT_RANDOM, arena
+    kinds = {Agent.MODEL: AGENT_MODEL, Agent.RANDOM: AGENT_RANDOM, Agent.MCTS: AGENT_MCTS}
+    types = (player1.player_type, player2.player_type)
+    if vanilla_rollouts is None:
+        vanilla_rollouts = Agent.MCTS in types and vanilla_rollouts_from_env()
+    if vanilla_rollouts and Agent.MODEL in types:
+        raise ValueError("Mcts with played rollouts against a Model agent: use play() (diee_arena has one quirks flag for both searches)")
     e1, e2 = player1.model, player2.model
     if e1 is None and e2 is None:
-        e1 = engine                            # two Random agents: any engine hosts the call
-    r = arena(e1, kinds[player1.player_type], e2, kinds[player2.player_type], num_games, mcts_config, temp, seed, round_limit, max_rounds)
+        e1 = engine                            # no player brings an engine (Random, Mcts): any engine hosts the call
+    r = arena(e1, kinds[player1.player_type], e2, kinds[player2.player_type], num_games, mcts_config, temp, seed, round_limit, max_rounds,
+              ref_quirks=not vanilla_rollouts)
     games = games_from_device(player1, player2, r["initial_states"], r["winner"], r["retired_round"], r["retired_side"])
     res = PlayResult(player1.player_type, player2.player_type, r["wins_p1"], r["wins_p2"], num_games, games)
     res.final_states = r["final_states"]
@@ -365,7 +399,8 @@ def play_tictactoe(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_gam
                     if vm:
                         acts[int(g)] = vm[min(int(uni[k] * len(vm)), len(vm) - 1)]
             else:
-                raise NotImplementedError("Agent::Mcts (vanilla MCTS with rollouts) is out of scope: SURVEY section 2 row 11")
+                raise NotImplementedError("Agent::Mcts (vanilla MCTS with rollouts) runs on the backgammon engine only; the tic-tac-toe "
+                                          "Mcts agent is not provided")
         round_count += 1                                                                 # :219
         for g in np.concatenate(sides):
             g = int(g)

@@ -85,7 +85,8 @@ typedef struct {
 /* flags */
 #define DIEE_FLAG_REF_QUIRKS 1u /* reproduce SURVEY Appendix A Q14 (stale selected_nodes_idxs
                                    slots, alpha_mcts.rs:142,157-166,175-200) and Q18 (double
-                                   flush, alpha_parallel.rs:172-180,215-223)                */
+                                   flush, alpha_parallel.rs:172-180,215-223); for Agent::Mcts
+                                   (diee_mcts_vanilla_batch) Q22: the rollout that plays nothing */
 #define DIEE_FLAG_INVARIANT_NN 2u /* evaluate every batch size with the fused 16x16x32 tower (one arithmetic
                                    for all sizes): the network output of a state is then a pure function of
                                    the state, whatever shares its launch.  Slower below 257 boards (the
@@ -194,6 +195,9 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *                                 a search whose ring would be larger runs one launch per iteration instead
  *   pinned_pool_mb        MiB of page-locked output blocks the PROCESS keeps for reuse after diee_free_fragments (default 8192;
  *                                 with several ranks per host: what each may retain)
+ *   vanilla_iters_per_launch   Agent::Mcts (diee_mcts_vanilla_batch, DIEE_AGENT_MCTS): iterations a game runs in one launch at most; the trees stay
+ *                                 in HBM from launch to launch and the results do not depend on it.  Default 0: derived from the call's
+ *                                 round_limit so that a launch stays far below a second (16384 / (round_limit + 1); 4096 under DIEE_FLAG_REF_QUIRKS)
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
  *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
  *                                 diee_self_play_refill of this ctx allocated: min(width, games of the call), whatever the call's length
@@ -234,6 +238,53 @@ diee_status diee_mcts_batch(diee_ctx*, const diee_bg_state* roots, uint32_t n,
                             const uint32_t* game_ids, const uint32_t* rounds, uint32_t flags,
                             float* visit_probs, uint32_t* n_children,
                             float* root_visits /* [n] or NULL */, diee_stats* stats);
+
+/* ---- level 1, Agent::Mcts: mct_search (src/mcts/simple_mcts.rs:10-39; Node, src/mcts/node.rs) for n roots, as get_actions_for_player calls
+ * it per game (versus.rs:303-306): vanilla UCB1 search with random rollouts, one wavefront per game, no network (the ctx needs no weights).
+ * Per root, player = root.player; cfg->iterations iterations of
+ *   select    from the root down while the node has children and no unexpanded play: the child of maximal
+ *             ucb = value / visits + sqrt((c * ln(parent.visits)) / visits) (node.rs:86-96; fp32, IEEE division and square root, this association),
+ *             of equal maxima the last created, NaN comparing Equal (as the PUCT selection does);
+ *   the selected node is a finished game: +1 if `player` won, -1 if the other side did, backpropagated from it (simple_mcts.rs:25-30);
+ *   it has an unexpanded play: its j-th child (j from 0) takes play number count - 1 - j of diee_bg_legal_moves' order (expandable_moves.pop(),
+ *             node.rs:118-137), apply_move with the dice below; simulate from the child, backpropagate from the child;
+ *   backpropagate   visits += 1, value += result on the node and every ancestor, the same sign at every level (simple_mcts.rs:96-103);
+ * the answer is the play of the root's most visited child, the last created of equal ones (:71-86); EMPTY_MOVE (all DIEE_NO_MOVE) if the root
+ * has no children.  simulate (node.rs:176-196), without DIEE_FLAG_REF_QUIRKS the rollout as it was meant: round_limit times { the state has a
+ * winner: return +-1 from `player`'s view; it has legal plays: plays[min(int(u * count), count - 1)], apply_move; otherwise skip_turn }, then 0
+ * (a state that became final on the last ply is not looked at, as in the reference's loop).  With DIEE_FLAG_REF_QUIRKS the reference's agent
+ * as written (the loop looks at the node's own state): +-1 if round_limit > 0 and the node simulated from is a
+ * finished game, otherwise 0; nothing is played.
+ * THE ENGINE'S CHOICES where the reference leaves the agent open:
+ *   a root that is a finished game, or has no legal play, runs no iteration and answers EMPTY_MOVE (the reference panics on the second at
+ *     node.rs:120; Agent::Random returns EMPTY_MOVE there, versus.rs:313);
+ *   a selected node that is not a finished game and has no legal play gets no children: every time it is selected the search simulates from
+ *     it and backpropagates from it, the rollout's first ply being its skip_turn (the reference panics in expand());
+ *   ln is not reproducible between a host's libm and the device: the host builds ln[k] = (float)log((double)k), k = 1 ... iterations + 1,
+ *     and the kernel reads it (visit counts are integers);
+ *   random numbers: Philox counter (game_id, round, TAG_VANILLA = 0xFFFFFFFB, iteration << 12 | k).  k = 0: the dice of the child created in
+ *     that iteration; k = 1 + p: rollout ply p -- its uniform picks the play, its dice are what apply_move / skip_turn is given.  Hence
+ *     iterations >= 2^20 or round_limit > 4094: DIEE_ERR_ARG.
+ * game_ids / rounds may be NULL (i / 0).  plays[n][4]; n_children[n] (or NULL) = the root's children; child_visits / child_values [n][cap]
+ * (or NULL) = their visits and values in creation order, zero beyond the count.  A launch runs a bounded number of iterations per game
+ * (option vanilla_iters_per_launch), the trees persist in HBM in between; the results do not depend on it.  More than 256 legal plays of
+ * one state: DIEE_ERR_CAPACITY.  A tic-tac-toe ctx: DIEE_ERR_UNSUPPORTED.  DIEE_FLAG_INVARIANT_NN is accepted and ignored. */
+typedef struct {
+    uint64_t iterations;       /* search iterations run, all roots                              */
+    uint64_t expansions;       /* children created                                              */
+    uint64_t terminal_hits;    /* selections ending on a finished game                          */
+    uint64_t dead_end_hits;    /* selections ending on a node without a legal play              */
+    uint64_t rollouts;         /* calls of simulate (expansions + dead_end_hits)                */
+    uint64_t rollout_plies;    /* plies played in them, skipped turns included                  */
+    uint64_t rollout_decided;  /* rollouts that returned +-1                                    */
+    uint64_t depth_sum;        /* sum of the selected nodes' depths                             */
+    double   seconds;          /* wall clock of the call                                        */
+} diee_vanilla_stats;
+
+diee_status diee_mcts_vanilla_batch(diee_ctx*, const diee_bg_state* roots, uint32_t n, const diee_mcts_cfg* cfg,
+                                    uint64_t seed, const uint32_t* game_ids, const uint32_t* rounds, uint32_t flags,
+                                    int8_t* plays, uint32_t* n_children, float* child_visits, float* child_values,
+                                    uint32_t cap, diee_vanilla_stats* stats);
 
 /* ---- level 2: AlphaZero::self_play_parallel, alpha_parallel.rs:101-231
  * n_games = num_self_play_batches; first_game_id offsets the RNG keys (rank * n_games when games
@@ -294,7 +345,9 @@ diee_status diee_self_play_refill(diee_ctx*, const diee_batch* batches, uint32_t
  *   diee_bg_legal_moves' order with the same uniform (:308-317).  A root without children, an all-zero row or no legal play skips the turn
  *   (skip_turn with the dice of (seed, i, round, TAG_MOVE_ROLL)) and that game is checked neither for a winner nor for the round limit in that
  *   round (:225-228); otherwise decode, apply_move with those dice, check_winner, and with no winner and round + 1 >= round_limit the game is
- *   retired as a draw (:233-237).  Agent::Mcts is not provided.
+ *   retired as a draw (:233-237).  DIEE_AGENT_MCTS (:303-306): the side's list is searched by diee_mcts_vanilla_batch's kernels with game_ids = i,
+ *   rounds = round and the call's seed and flags; its answer goes through the same skip / apply / winner / round-limit step.  `temperature` is
+ *   not used by it, and its ctx may be NULL under the rule of a Random agent's.
  * The call runs on p1's stream, slots and tree arena with p1's search options (free_eval, spec_eval, shared_gpu, ...); for player 2's searches
  * it borrows p2's network -- weights, activations, dispatch tables -- and touches nothing else of p2.  p2 on another device: DIEE_ERR_ARG;
  * p2 == p1 is allowed; the ctx of a Random agent may be NULL as long as the other one is not (then that one hosts the call).  A Model agent
@@ -306,9 +359,11 @@ diee_status diee_self_play_refill(diee_ctx*, const diee_batch* batches, uint32_t
  * stats[2], per player: the search counters of that player's searches (expansions, selections, nn_evals, ...); seconds = the call's wall clock;
  * move_steps = its searches; plies = the turns it took, skipped ones included; fragments = the turns in which a move was applied (plies -
  * fragments = skipped turns); games = games retired by one of its moves; band_launches[b] = its turns whose list had a size in band b
- * (DIEE_BANDS).  The tail_* totals of the call are reported with player 1. */
+ * (DIEE_BANDS).  The tail_* totals of the call are reported with player 1.  A DIEE_AGENT_MCTS player fills selections (= iterations),
+ * expansions, terminal_hits, depth_sum, move_steps, plies, fragments, games, band_launches and seconds; the network fields are 0. */
 #define DIEE_AGENT_RANDOM 0   /* Agent::Random, versus.rs:308-317 */
 #define DIEE_AGENT_MODEL  1   /* Agent::Model,  versus.rs:279-306 */
+#define DIEE_AGENT_MCTS   2   /* Agent::Mcts,   versus.rs:303-306 */
 
 typedef struct {
     uint32_t wins_p1, wins_p2, draws;   /* PlayResult, versus.rs:129-152 */

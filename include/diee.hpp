@@ -98,6 +98,19 @@ public:
         return r;
     }
 
+    // mct_search(&state, &cfg) per root (simple_mcts.rs:10-39), Agent::Mcts: vanilla UCB1 search with random rollouts; needs no weights.
+    // ref_quirks: the reference's rollout, which plays nothing (Q22).  -> the plays (EMPTY_MOVE: all DIEE_NO_MOVE)
+    std::vector<Play> mct_search(const std::vector<Backgammon>& states, const MctsConfig& cfg, uint64_t seed, bool ref_quirks = true,
+                                 diee_vanilla_stats* stats = nullptr) {
+        std::vector<int8_t> plays(states.size() * 4);
+        chk(diee_mcts_vanilla_batch(ctx_, states.data(), (uint32_t)states.size(), &cfg, seed, nullptr, nullptr,
+                                    ref_quirks ? DIEE_FLAG_REF_QUIRKS : 0u, plays.data(), nullptr, nullptr, nullptr, 0, stats));
+        std::vector<Play> out(states.size());
+        for (size_t i = 0; i < states.size(); ++i)
+            for (int k = 0; k < 4; ++k) out[i].mv[k] = plays[i * 4 + k];
+        return out;
+    }
+
     // self_play_parallel: num_self_play_batches games to completion -> Vec<MemoryFragment>
     std::vector<MemoryFragment> self_play_parallel(uint32_t num_self_play_batches, const MctsConfig& cfg, float temperature, uint64_t seed,
                                                    diee_stats* stats = nullptr, bool ref_quirks = true) {
@@ -139,7 +152,7 @@ public:
     }
 
     // play() of versus.rs:160-268 in one engine call (diee_arena): this engine is player 1 (side -1 in every game) and hosts the call,
-    // `player2` lends its network.  A null player2 with agent2 = DIEE_AGENT_RANDOM is a random opponent.
+    // `player2` lends its network.  A null player2 with agent2 = DIEE_AGENT_RANDOM is a random opponent, with DIEE_AGENT_MCTS the vanilla search.
     struct ArenaResult {
         diee_arena_result result;
         std::vector<int8_t> winner, retired_side;                // per game: -1 player 1, +1 player 2, 0 none; the list it moved in when retired
