@@ -265,6 +265,9 @@ diee_status diee_mcts_batch(diee_ctx*, const diee_bg_state* roots, uint32_t n,
  *   random numbers: Philox counter (game_id, round, TAG_VANILLA = 0xFFFFFFFB, iteration << 12 | k).  k = 0: the dice of the child created in
  *     that iteration; k = 1 + p: rollout ply p -- its uniform picks the play, its dice are what apply_move / skip_turn is given.  Hence
  *     iterations >= 2^20 or round_limit > 4094: DIEE_ERR_ARG.
+ * cfg->c is not checked: a negative, infinite or NaN exploration constant is served as the reference's arithmetic would serve it -- a score
+ *   that is NaN compares Equal in select_child's max_by (simple_mcts.rs:46-51), so the choice is the best child created after the last one
+ *   whose score is NaN, or that one if it is the last.
  * game_ids / rounds may be NULL (i / 0).  plays[n][4]; n_children[n] (or NULL) = the root's children; child_visits / child_values [n][cap]
  * (or NULL) = their visits and values in creation order, zero beyond the count.  A launch runs a bounded number of iterations per game
  * (option vanilla_iters_per_launch), the trees persist in HBM in between; the results do not depend on it.  More than 256 legal plays of

@@ -76,6 +76,22 @@ def test_play_serves_an_mcts_player_through_a_search_object(oracle):
         versus.play_tictactoe(P(versus.Agent.MCTS), P(versus.Agent.RANDOM), cfg, 1.25, num_games=2)
 
 
+def test_edge_case_roots_meet_their_preconditions(oracle):
+    """tests/vanilla_cases.py: the roots of tests/test_vanilla_edges_gpu.py have the play counts the cases are about, and the
+    restatement alone takes the paths they are about -- selection through roots wider than a wavefront, scores that are NaN where
+    that changes the answer, rollouts of zero, one and two plies"""
+    import vanilla_cases as vc
+    assert len(vc.wide_roots()) == 6 and len(vc.const_roots()) == 5          # (the builders assert the play counts and off = [5, 6])
+    for quirks in (True, False):
+        beyond = vc.check_wide(quirks)
+        print(vc.line(f"wide roots, quirks {'on' if quirks else 'off'}, {beyond} descents beyond depth 1", vc.wide_reference(quirks)["stats"]))
+    differ = vc.check_consts()
+    print(vc.line(f"c = -1.0 (differs from c = 0.0 on roots {differ})", vc.const_reference(-1.0)["stats"]))
+    print(vc.line("c = 0.0", vc.const_reference(0.0)["stats"]))
+    for rl, st in vc.check_limits().items():
+        print(vc.line(f"round_limit {rl}, quirks off", st))
+
+
 @pytest.mark.parametrize("quirks", [True, False])
 def test_invariants_of_the_restatement(oracle, quirks):
     from vanilla_ref import mct_search
