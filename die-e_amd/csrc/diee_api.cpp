@@ -4,6 +4,7 @@
 #include "engine.h"
 #include "nn_host.h"
 #include "launch.h"
+#include "pinned_pool.h"
 #include "ttt_host.h"
 
 #include <mutex>
@@ -167,12 +168,6 @@ diee_status diee_probe_dice(diee_ctx* c, uint64_t seed, const uint32_t* ctr, uin
 }  // extern "C"
 
 // ---- network / search entry points ---------------------------------------------------------------
-namespace diee {
-size_t weights_count_bg();
-void random_weights_bg(uint64_t seed, float* blob);
-bool pinned_release(void* p);   // search_host.cpp: back to the pool of page-locked blocks; false = not one of its blocks
-}
-
 extern "C" {
 
 size_t diee_weights_count(int game_id) {
@@ -418,7 +413,7 @@ diee_status diee_train_colsum(const void* a, float* out, int rows, float* scratc
 
 void diee_free_fragments(diee_fragments* f) {
     if (!f) return;
-    // the backgammon engine hands out page-locked blocks of its pool (search_host.cpp), the tic-tac-toe host path malloc'ed ones
+    // the backgammon engine hands out page-locked blocks of its pool (pinned_pool.cpp), the tic-tac-toe host path malloc'ed ones
     void* ps[4] = {f->outcome, f->ps, f->state, f->game};
     for (void* p : ps) if (!diee::pinned_release(p)) free(p);
     memset(f, 0, sizeof *f);

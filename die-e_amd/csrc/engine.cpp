@@ -7,17 +7,10 @@
 #include <vector>
 
 #include "launch.h"
+#include "search_host.h"
+#include "vanilla_host.h"
 
 namespace diee {
-
-void free_net(NetWeights*);
-void cluster_baton_register(int device, int delta);
-void nn_reset_cluster(Engine& e);
-void nn_disable_cluster(Engine& e);
-void free_search(SearchBufs*);
-void free_vanilla(VanillaBufs*);
-void pinned_pool_set_cap_mb(size_t mb);
-size_t pinned_pool_cap_mb();
 
 // ---- options ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -45,7 +38,7 @@ const OptEntry kOptions[] = {
     {"deliver_stage_rows", nullptr, &Options::deliver_stage_rows, nullptr}, {"deliver_rows_per_game", nullptr, &Options::deliver_rows_per_game, nullptr},
     {"trace_steps", &Options::trace_steps, nullptr, nullptr}, {"trace_dispatch", &Options::trace_dispatch, nullptr, nullptr},
     {"test_starve_at", &Options::test_starve_at, nullptr, nullptr}, {"test_tail_skip", &Options::test_tail_skip, nullptr, nullptr},
-    {"pinned_pool_mb", nullptr, nullptr, nullptr},          // process-wide: the cap of the pool of page-locked output blocks (search_host.cpp)
+    {"pinned_pool_mb", nullptr, nullptr, nullptr},          // process-wide: the cap of the pool of page-locked output blocks (pinned_pool.cpp)
 };
 const char kRefillAreas[] = "refill_record_areas";          // read-only: record areas the last diee_self_play_refill allocated
 const OptEntry* find_option(const std::string& key) {

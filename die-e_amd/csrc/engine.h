@@ -42,7 +42,7 @@ struct DevBuf {
 };
 
 struct NetWeights;   // nn_host.cpp
-struct SearchBufs;   // search_host.cpp
+struct SearchBufs;   // search_host.h
 struct VanillaBufs;  // vanilla_host.cpp
 
 // Per-ctx switches (diee_set_option, include/diee.h).  Defaults here; the environment (DIEE_<KEY IN CAPITALS>, e.g. DIEE_TOWER_CL for

@@ -110,6 +110,7 @@ void launch_reduce_counters(hipStream_t st, const Slots& S, const Segs& G, unsig
 void launch_row_map(hipStream_t st, const uint8_t* skip, uint32_t n, uint32_t* row_slot, uint32_t* slot_row, uint32_t* n_rows,
                     uint32_t* rows_log, uint32_t log_idx);
 void launch_root_probs(hipStream_t st, const Tree& T, uint32_t n, float* probs, uint32_t* nch, float* root_visits);
+// selfplay_kernels.hip (search_types.h, Games): the games of a self-play call around their move-steps' searches
 void launch_init_games(hipStream_t st, const Games& Gm, const Segs& G, uint32_t n);
 void launch_gather_roots(hipStream_t st, const Games& Gm, const Slots& S, const Segs& G, uint32_t n_live);
 void launch_play_move(hipStream_t st, const Tree& T, const Games& Gm, const Segs& G, uint32_t n_live, uint32_t step, const PlayParams& P);

@@ -81,7 +81,7 @@ struct NetWeights {
     bool compact = true;            // search iterations above compact_above live games evaluate only the slots that need it (k_row_map)
     int compact_above = 256;        // (below, the batch is latency-bound and runs whole on the cluster tower)
     DevBuf<uint32_t> rows_log;      // [kRowsLog] rows evaluated by the compacted forward number (forward_count mod kRowsLog)
-    int cur_step = -1;              // the move-step whose search is being enqueued (search_host.cpp; -1: none): a sampled launch remembers it
+    int cur_step = -1;              // the move-step whose search is being enqueued (selfplay_host.cpp; -1: none): a sampled launch remembers it
     DevBuf<uint32_t> dem_log;       // [kRowsLog] ... of which DEMANDED by the search (tail / free-running launches: the others are speculative)
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
@@ -108,6 +108,10 @@ constexpr uint32_t kRowsLog = 1u << 20;
 // device-side description of a compacted batch (owned by the search): skip[slot] != 0 = no evaluation needed;
 // k_row_map fills row_slot / slot_row / n_rows right before the network launches
 struct NnRows { const uint8_t* skip; uint32_t* row_slot; uint32_t* slot_row; uint32_t* n_rows; };
+void free_net(NetWeights* n);
+void cluster_baton_register(int device, int delta);      // ctxs of this process on `device` (+1 / -1)
+size_t weights_count_bg();
+void random_weights_bg(uint64_t seed, float* blob);
 void nn_reserve(Engine& e, int G);
 // policy_dev == nullptr: stop after the policy FC and the head convs; the caller (the search) finishes the softmax and the
 // value head itself from nn_heads() with the functions of nn_device.h (same bits, one launch less per evaluation)

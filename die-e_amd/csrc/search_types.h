@@ -1,5 +1,5 @@
-// search_types.h -- kernel parameter blocks (plain device pointers) shared by mcts_kernels.hip and
-// the host driver.  Layout in HBM:
+// search_types.h -- kernel parameter blocks (plain device pointers) shared by mcts_kernels.hip, selfplay_kernels.hip and
+// the host drivers.  Layout in HBM:
 //   Tree   : one fixed-stride arena per live-game slot (slot*node_cap + local index); node statistics
 //            are SoA so that a wave reading the children of a node issues coalesced 4-byte loads;
 //            children of a node are contiguous (first_child, n_children).
@@ -127,7 +127,7 @@ struct DeliverOut { float* ps; float* planes; int8_t* outcome; uint32_t* game; }
 // earlier needs NO launch: k_tail (mcts_kernels.hip) runs the iterations of all live games in lockstep, one after the other inside
 // one launch, for as long as every selected leaf is in the ring, and plans the next launch's rows when one is not.  The search
 // itself -- selection, expansion, backpropagation, the quirks' coupling of the games of a batch -- is the same code on the same
-// numbers in the same order (expand_body): results are bit-identical to the launch-per-iteration path, which remains above spec_max_games (96) games.
+// numbers in the same order (expand_body): results are bit-identical to the launch-per-iteration path.  It ships for <= 16 live games: the free-running search below takes 17 ... 800.
 // What rides in a launch beside the demanded leaves: every game's share of candidates (virtual descents), the candidates beyond the shares
 // where rows are scarce (extra_rows: they take what other games leave free), and the children of a demanded leaf (child_rows: the one
 // parent whose expanding iteration -- the key of its children's dice -- is known before it is expanded).
@@ -161,7 +161,7 @@ struct Tail {
                             // spin runs out, the starved bit is raised, the host repeats the move-step's search launch by launch
 };
 
-// ---- free-running search (round 6): 257 ... 928 live games ---------------------------------------------------------------------------
+// ---- free-running search (round 6): 17 ... 800 live games (k_tail keeps <= 16) ---------------------------------------------------------------------------
 // Above the tail's reach every MCTS iteration used to cost one network launch sized by the live games -- 300 us for <= 512 boards,
 // ~480 ... 520 us for 513 ... 928, 577 us for a full pass of the chip: the rows of a part-empty launch cost up to twice a full one's.  The
 // reference couples the games of a call only through `node_selected` (alpha_mcts.rs:151,170) and the stale slots (:142,192-200), so
@@ -193,7 +193,7 @@ struct Free {
     uint32_t* state;        // [0] all games done, [1] launches that carried rows, [2] rows evaluated on speculation, [4] games not done when the last round was
                             // packed (k_free sizes its budgets by them: the last games of a search have the launches to themselves)
     uint32_t* host;         // pinned: [0] done, [1] last k_free_pack that finished
-    uint32_t launches;      // rounds the host sends at most: 4 x (iterations + games) + 66 (search_host.cpp free_view)
+    uint32_t launches;      // rounds the host sends at most: 4 x (iterations + games) + 66 (search_host.cpp free_launches_for)
     uint32_t iterations;
     uint32_t rows;          // rows of a launch at most (512: pair tower; 1024: one pass of the chip)
     uint32_t ring;          // launches whose rows stay in the ring

@@ -14,9 +14,9 @@
 
 #include "bg_device.h"
 #include "engine.h"
+#include "search_host.h"
 
 namespace diee {
-void dirichlet_host(uint64_t seed, uint32_t step, float alpha, int n, float* out);     // search_host.cpp
 namespace ttt {
 
 // ---- rules -----------------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ Vanilla vanilla_reserve(Engine& e, uint32_t n, const diee_mcts_cfg& cfg, uint64_
 void vanilla_search(Engine& e, const Vanilla& V, uint32_t n, uint32_t* n_children = nullptr, float* child_visits = nullptr,
                     float* child_values = nullptr, uint32_t cap = 0);
 void vanilla_zero_counters(Engine& e);
+void free_vanilla(VanillaBufs* v);
 void vanilla_read_counters(Engine& e, uint32_t side, diee_vanilla_stats* out);      // waits for the stream
 
 }  // namespace diee
