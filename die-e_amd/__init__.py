@@ -49,7 +49,7 @@ assert TTT_STATE.itemsize == 32
 EXPORTS = [
     "diee_create", "diee_destroy", "diee_last_error", "diee_version", "diee_set_option", "diee_get_option", "diee_device_pci_bus_id", "diee_weights_count",
     "diee_random_weights", "diee_load_weights", "diee_nn_forward", "diee_mcts_batch", "diee_mcts_vanilla_batch", "diee_self_play",
-    "diee_self_play_multi", "diee_self_play_refill", "diee_arena", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
+    "diee_self_play_multi", "diee_self_play_refill", "diee_arena", "diee_arena_ex", "diee_free_arena_log", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
     "diee_train_conv3x3", "diee_train_im2col3x3",
     "diee_train_scratch_floats", "diee_train_bn_relu_fwd", "diee_train_bn_relu_bwd", "diee_train_colsum",
     "diee_train_set_bn_coop", "diee_train_bn_coop_timeouts",
@@ -107,6 +107,27 @@ class ArenaResult(C.Structure):
     """diee_arena_result"""
     _fields_ = [("wins_p1", C.c_uint32), ("wins_p2", C.c_uint32), ("draws", C.c_uint32), ("rounds", C.c_uint32),
                 ("illegal_decodes", C.c_uint64), ("seconds", C.c_double)]
+
+
+class Turn(C.Structure):
+    """diee_turn: one turn of the arena's log (Turn, versus.rs:21-26, + next_roll and second)"""
+    _fields_ = [("play", C.c_int8 * 4), ("roll", C.c_uint8 * 2), ("next_roll", C.c_uint8 * 2), ("player", C.c_int8),
+                ("agent", C.c_uint8), ("second", C.c_uint8), ("retired", C.c_uint8)]
+
+
+TURN = np.dtype([("play", "i1", 4), ("roll", "u1", 2), ("next_roll", "u1", 2), ("player", "i1"), ("agent", "u1"),
+                 ("second", "u1"), ("retired", "u1")])
+assert TURN.itemsize == 12 == C.sizeof(Turn)
+
+
+class ArenaLog(C.Structure):
+    """diee_arena_log: game g's turns are turns[first[g] .. first[g + 1]); the engine's until diee_free_arena_log"""
+    _fields_ = [("turns", C.POINTER(Turn)), ("first", C.POINTER(C.c_uint64)), ("n_games", C.c_uint32), ("owner", C.c_void_p)]
+
+
+class ArenaOpts(C.Structure):
+    """diee_arena_opts"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32 * 2), ("log", C.POINTER(ArenaLog))]
 
 
 class VanillaStats(C.Structure):
@@ -173,6 +194,8 @@ def load_library(path=None):
     L.diee_self_play_multi.argtypes = [vp, vp, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_multi.restype = C.c_int
     L.diee_self_play_refill.argtypes = [vp, vp, u32, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_refill.restype = C.c_int
     L.diee_arena.argtypes = [vp, C.c_int, vp, C.c_int, u32, vp, f32, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]; L.diee_arena.restype = C.c_int
+    L.diee_arena_ex.argtypes = [vp, C.c_int, vp, C.c_int, u32, vp, f32, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]; L.diee_arena_ex.restype = C.c_int
+    L.diee_free_arena_log.argtypes = [vp]; L.diee_free_arena_log.restype = None
     L.diee_set_invariant_nn.argtypes = [vp, C.c_int]; L.diee_set_invariant_nn.restype = C.c_int
     L.diee_train_pack_conv3x3.argtypes = [vp, vp, C.c_int, vp]; L.diee_train_pack_conv3x3.restype = C.c_int
     L.diee_train_pack_conv3x3_multi.argtypes = [C.POINTER(vp), C.c_int, vp, vp]; L.diee_train_pack_conv3x3_multi.restype = C.c_int
@@ -517,19 +540,22 @@ class Engine:
         return self._take_batches(frs, sts, fetch, copy)
 
     def arena(self, agent1, other, agent2, n_games, cfg, temperature=1.25, seed=0xD1EE0001, round_limit=400, max_rounds=0,
-              ref_quirks=True, invariant_nn=False):
+              ref_quirks=True, invariant_nn=False, record_turns=False, flags2=None):
         """arena() below with this engine as player 1"""
-        return arena(self, agent1, other, agent2, n_games, cfg, temperature, seed, round_limit, max_rounds, ref_quirks, invariant_nn)
+        return arena(self, agent1, other, agent2, n_games, cfg, temperature, seed, round_limit, max_rounds, ref_quirks, invariant_nn,
+                     record_turns, flags2)
 
 
 def arena(engine1, agent1, engine2, agent2, n_games, cfg, temperature=1.25, seed=0xD1EE0001, round_limit=400, max_rounds=0,
-          ref_quirks=True, invariant_nn=False):
+          ref_quirks=True, invariant_nn=False, record_turns=False, flags2=None):
     """play() of versus.rs:160-268 in one engine call (diee_arena).  engine1 is player 1 (side -1 in every game) and hosts the call,
     engine2 (an Engine on the same device, engine1 again, or None for a Random agent) lends player 2's network; engine1 may be None
     for a Random or Mcts agent, then engine2 hosts.  agent1 / agent2: AGENT_MODEL | AGENT_RANDOM | AGENT_MCTS.  -> dict(wins_p1, wins_p2, draws, rounds,
     illegal_decodes, seconds, winner int8 [n], retired_round uint32 [n] (0xFFFFFFFF: still alive, max_rounds), retired_side int8 [n],
     initial_states, final_states, stats [per player]); raises if a sampled action did not decode to a valid move (versus.rs:229
-    panics)"""
+    panics).  record_turns / flags2 go through diee_arena_ex: record_turns adds `turns` (a TURN array, every turn of every game) and
+    `first` (uint64 [n + 1]: game g's turns are turns[first[g]:first[g + 1]] in play order); flags2 is the flag word (FLAG_*) of
+    player 2's searches where it differs from player 1's (ref_quirks / invariant_nn); None: the same word."""
     host = engine1 if engine1 is not None else engine2
     if host is None:
         raise ValueError("the arena needs an engine")
@@ -538,15 +564,31 @@ def arena(engine1, agent1, engine2, agent2, n_games, cfg, temperature=1.25, seed
     init = np.zeros(n, dtype=BG_STATE); final = np.zeros(n, dtype=BG_STATE)
     res = ArenaResult(); sts = (Stats * 2)()
     flags = (FLAG_REF_QUIRKS if ref_quirks else 0) | (FLAG_INVARIANT_NN if invariant_nn else 0)
-    host._chk(host._L.diee_arena(None if engine1 is None else engine1._h, int(agent1), None if engine2 is None else engine2._h, int(agent2),
-                                 n, C.byref(cfg), temperature, seed, int(round_limit), int(max_rounds), flags, C.byref(res),
-                                 winner.ctypes.data, rround.ctypes.data, rside.ctypes.data, init.ctypes.data, final.ctypes.data,
-                                 C.byref(sts)))
+    h1, h2 = None if engine1 is None else engine1._h, None if engine2 is None else engine2._h
+    outs = (C.byref(res), winner.ctypes.data, rround.ctypes.data, rside.ctypes.data, init.ctypes.data, final.ctypes.data, C.byref(sts))
+    extra = {}
+    if not record_turns and flags2 is None:
+        host._chk(host._L.diee_arena(h1, int(agent1), h2, int(agent2), n, C.byref(cfg), temperature, seed, int(round_limit), int(max_rounds),
+                                     flags, *outs))
+    else:
+        log = ArenaLog()
+        opts = ArenaOpts(C.sizeof(ArenaOpts), (C.c_uint32 * 2)(flags, flags if flags2 is None else int(flags2)),
+                         C.pointer(log) if record_turns else None)
+        host._chk(host._L.diee_arena_ex(h1, int(agent1), h2, int(agent2), n, C.byref(cfg), temperature, seed, int(round_limit),
+                                        int(max_rounds), C.byref(opts), *outs))
+        if record_turns:
+            first = np.ctypeslib.as_array(log.first, shape=(n + 1,)).copy()
+            total = int(first[n])
+            turns = np.zeros(total, dtype=TURN)
+            if total:
+                C.memmove(turns.ctypes.data, log.turns, total * TURN.itemsize)
+            host._L.diee_free_arena_log(C.byref(log))
+            extra = {"turns": turns, "first": first}
     if res.illegal_decodes:
         raise DieeError(ERR_CAPACITY, f"decoded action is not a valid move ({res.illegal_decodes} illegal decodes)")
     return {"wins_p1": res.wins_p1, "wins_p2": res.wins_p2, "draws": res.draws, "rounds": res.rounds,
             "illegal_decodes": res.illegal_decodes, "seconds": res.seconds, "winner": winner, "retired_round": rround,
-            "retired_side": rside, "initial_states": init, "final_states": final, "stats": [sts[0].as_dict(), sts[1].as_dict()]}
+            "retired_side": rside, "initial_states": init, "final_states": final, "stats": [sts[0].as_dict(), sts[1].as_dict()], **extra}
 
 
 # ---- LearnableGame for TicTacToe (src/tictactoe/mod.rs), host functions of the C ABI -------------------------------------

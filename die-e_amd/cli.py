@@ -175,19 +175,16 @@ def main(argv=None):
             m1 = eng
         if a2 == Agent.MCTS and m2 is None:
             m2 = eng
-        from .versus import vanilla_rollouts_from_env
+        from .versus import record_turns_from_env, vanilla_rollouts_from_env
         rollouts = Agent.MCTS in (a1, a2) and vanilla_rollouts_from_env()
-        on_device = os.environ.get("DIEE_ARENA") == "device"
-        if on_device and rollouts and Agent.MODEL in (a1, a2):
-            sys.stderr.write("[diee] DIEE_ARENA=device not used: Mcts with played rollouts against a Model agent runs on the host driver\n")
-            on_device = False
-        if on_device:                                                                         # every round on the device (diee_arena): the same result
+        record = record_turns_from_env()                                                      # DIEE_RECORD_TURNS=1: the saved games carry their turns (Q21)
+        if os.environ.get("DIEE_ARENA") == "device":                                          # every round on the device (diee_arena): the same result
             from .versus import play_device
             res = play_device(Player(a1, m1), Player(a2, m2), mcts_config_from(conf), float(conf["temperature"]), engine=eng,
-                              vanilla_rollouts=rollouts)
+                              vanilla_rollouts=rollouts, record_turns=record)
         else:
             res = play(Player(a1, m1), Player(a2, m2), mcts_config_from(conf), float(conf["temperature"]),
-                       rules=EngineRules(m1 or m2 or eng), vanilla_rollouts=rollouts)
+                       rules=EngineRules(m1 or m2 or eng), vanilla_rollouts=rollouts, record_turns=record)
         print(f"{res}\n Saving games...")
         for g in res.games:
             save_game(g, args.output_path)

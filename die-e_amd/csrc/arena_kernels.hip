@@ -122,9 +122,17 @@ __global__ __launch_bounds__(64) void k_arena_move(Tree T, Arena A, uint32_t n, 
     int d0, d1;
     draw_dice(P.seed, g, P.round, kTagMoveRoll, 0u, d0, d1);
     atomicAdd(&A.words[AW_TURNS0 + P.side], 1u);
+    ArenaTurn rec{};                                          // Turn { roll, action, player }, versus.rs:21-26, + what makes it replayable
+    if (P.log) {
+        rec.play[0] = (int8_t)play_f1(play); rec.play[1] = (int8_t)play_t1(play); rec.play[2] = (int8_t)play_f2(play); rec.play[3] = (int8_t)play_t2(play);
+        rec.roll[0] = (uint8_t)st_roll(s, 0); rec.roll[1] = (uint8_t)st_roll(s, 1);
+        rec.next_roll[0] = (uint8_t)d0; rec.next_roll[1] = (uint8_t)d1;
+        rec.player = (int8_t)st_player(s); rec.agent = (uint8_t)P.agent; rec.second = (uint8_t)st_second(s); rec.retired = 0;
+    }
     if (play_f1(play) == kNoMove) {                             // :225-228 skip_turn; continue (no winner / round-limit check)
         bg_skip_dev(s, d0, d1);
         store_state(&A.state[g], s);
+        if (P.log) P.log[g] = rec;
         return;
     }
     bg_apply_dev(s, play, d0, d1);                              // :230
@@ -136,7 +144,9 @@ __global__ __launch_bounds__(64) void k_arena_move(Tree T, Arena A, uint32_t n, 
         A.retired_round[g] = P.round; A.retired_side[g] = (int8_t)P.side;
         atomicAdd(&A.words[w < 0 ? AW_WINS1 : w > 0 ? AW_WINS2 : AW_DRAWS], 1u);
         atomicAdd(&A.words[AW_RETIRED0 + P.side], 1u);
+        rec.retired = 1;
     }
+    if (P.log) P.log[g] = rec;                                  // g < n_games = the records of a row
 }
 
 // ---- host launchers -----------------------------------------------------------------------------

@@ -272,17 +272,34 @@ diee_status diee_arena(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2, uint3
                        uint64_t seed, uint32_t round_limit, uint32_t max_rounds, uint32_t flags, diee_arena_result* res, int8_t* winner,
                        uint32_t* retired_round, int8_t* retired_side, diee_bg_state* initial_states, diee_bg_state* final_states,
                        diee_stats* stats) {
+    const diee_arena_opts opts{(uint32_t)sizeof(diee_arena_opts), {flags, flags}, nullptr};
+    return diee_arena_ex(p1, agent1, p2, agent2, n_games, cfg, temperature, seed, round_limit, max_rounds, &opts, res, winner, retired_round,
+                         retired_side, initial_states, final_states, stats);
+}
+
+diee_status diee_arena_ex(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2, uint32_t n_games, const diee_mcts_cfg* cfg, float temperature,
+                          uint64_t seed, uint32_t round_limit, uint32_t max_rounds, const diee_arena_opts* opts, diee_arena_result* res,
+                          int8_t* winner, uint32_t* retired_round, int8_t* retired_side, diee_bg_state* initial_states,
+                          diee_bg_state* final_states, diee_stats* stats) {
     diee_ctx* c = p1 ? p1 : p2;                                  // the ctx that hosts the call (stream, slots, tree arena, options, error text)
     API_BEGIN(c)
-    if (!cfg) throw EngineError(DIEE_ERR_ARG, "null pointer");
+    if (!cfg || !opts) throw EngineError(DIEE_ERR_ARG, "null pointer");
+    if (opts->struct_size != sizeof(diee_arena_opts)) throw EngineError(DIEE_ERR_ARG, "diee_arena_opts.struct_size is not sizeof(diee_arena_opts)");
+    if (opts->log) memset(opts->log, 0, sizeof *opts->log);      // (whatever follows: freeing it is harmless)
     Engine* host = bg(c);
     Engine* e1 = p1 ? bg(p1) : nullptr;
     Engine* e2 = p2 ? bg(p2) : nullptr;
     if (e1 && e2 && e1->device != e2->device) throw EngineError(DIEE_ERR_ARG, "the two ctxs of an arena call must be on the same device");
     if ((agent1 == DIEE_AGENT_MODEL && !e1) || (agent2 == DIEE_AGENT_MODEL && !e2)) throw EngineError(DIEE_ERR_ARG, "a Model agent needs its ctx");
-    host->arena(e1 ? e1->net : nullptr, agent1, e2 ? e2->net : nullptr, agent2, n_games, cfg, temperature, seed, round_limit, max_rounds, flags,
-                res, winner, retired_round, retired_side, initial_states, final_states, stats);
+    host->arena(e1 ? e1->net : nullptr, agent1, e2 ? e2->net : nullptr, agent2, n_games, cfg, temperature, seed, round_limit, max_rounds, opts->flags,
+                opts->log, res, winner, retired_round, retired_side, initial_states, final_states, stats);
     API_END(c)
+}
+
+void diee_free_arena_log(diee_arena_log* l) {
+    if (!l) return;
+    free(l->owner);                                              // one block: first[], then the turns
+    memset(l, 0, sizeof *l);
 }
 
 diee_status diee_dev_conv_bench(diee_ctx* c, int G, int variant, int reps, float* us_mode0, float* us_mode1,

@@ -34,6 +34,7 @@ const OptEntry kOptions[] = {
     {"free_ring", nullptr, &Options::free_ring, nullptr}, {"free_iter_cap", nullptr, &Options::free_iter_cap, nullptr}, {"free_cand_x4", nullptr, &Options::free_cand_x4, nullptr},
     {"free_lag_boost", nullptr, &Options::free_lag_boost, nullptr}, {"free_lag_step", nullptr, &Options::free_lag_step, nullptr}, {"free_lds_nodes", nullptr, &Options::free_lds_nodes, nullptr},
     {"vanilla_iters_per_launch", nullptr, &Options::vanilla_iters_per_launch, nullptr},
+    {"arena_log_rounds", nullptr, &Options::arena_log_rounds, nullptr}, {"arena_log_mb", nullptr, &Options::arena_log_mb, nullptr},
     {"path_cap", nullptr, &Options::path_cap, nullptr}, {"nodes_per_expansion", nullptr, &Options::nodes_per_expansion, nullptr},
     {"deliver_stage_rows", nullptr, &Options::deliver_stage_rows, nullptr}, {"deliver_rows_per_game", nullptr, &Options::deliver_rows_per_game, nullptr},
     {"trace_steps", &Options::trace_steps, nullptr, nullptr}, {"trace_dispatch", &Options::trace_dispatch, nullptr, nullptr},

@@ -83,6 +83,8 @@ struct Options {
                                             // would be larger runs one launch per iteration instead (iterations = 1600 x 512 rows: 4.7 GB)
     uint32_t path_cap = 64, nodes_per_expansion = 128;
     uint32_t vanilla_iters_per_launch = 0;  // Agent::Mcts: iterations a game runs per launch at most; 0: derived from round_limit (vanilla_host.cpp) -- same results
+    uint32_t arena_log_rounds = 64;         // the arena's turn log: rounds per chunk of its device rows (tests lower it to cross chunk boundaries) -- same log
+    uint32_t arena_log_mb = 1024;           // ... and the HBM (MiB) the log of one call may take: a round beyond it is not played (DIEE_ERR_CAPACITY)
     // output delivery
     uint32_t deliver_stage_rows = 16384, deliver_rows_per_game = 128;
     // development traces on stderr
@@ -123,8 +125,9 @@ public:
                           uint32_t flags, uint32_t max_steps, diee_fragments* outs, diee_stats* stats);
     // the arena (versus.rs:160-318): this ctx hosts the call; net1 / net2 = the networks of the two players' ctxs (null for a Random agent)
     void arena(NetWeights* net1, int agent1, NetWeights* net2, int agent2, uint32_t n_games, const diee_mcts_cfg* cfg, float temperature,
-               uint64_t seed, uint32_t round_limit, uint32_t max_rounds, uint32_t flags, diee_arena_result* res, int8_t* winner,
-               uint32_t* retired_round, int8_t* retired_side, diee_bg_state* initial_states, diee_bg_state* final_states, diee_stats* stats);
+               uint64_t seed, uint32_t round_limit, uint32_t max_rounds, const uint32_t flags[2] /* per player */, diee_arena_log* log /* null: none */,
+               diee_arena_result* res, int8_t* winner, uint32_t* retired_round, int8_t* retired_side, diee_bg_state* initial_states,
+               diee_bg_state* final_states, diee_stats* stats);
     // Agent::Mcts: mct_search (simple_mcts.rs:10-39) for n roots; needs no weights (vanilla_host.cpp)
     void mcts_vanilla_batch(const diee_bg_state* roots, uint32_t n, const diee_mcts_cfg* cfg, uint64_t seed, const uint32_t* game_ids,
                             const uint32_t* rounds, uint32_t flags, int8_t* plays, uint32_t* n_children, float* child_visits,

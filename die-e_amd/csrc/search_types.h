@@ -241,12 +241,27 @@ struct Arena {
     uint32_t* words;        // [AW_COUNT]
     uint32_t n_games;
 };
+// The turn log (diee_arena_ex; Turn, versus.rs:21-26): one record per turn, the layout of diee_turn (include/diee.h).  k_arena_split puts
+// every live game into exactly one side's list, so a live game takes exactly one turn per round and its turn index IS the call's round:
+// the log is round-major rows of n_games records, game g's turn of round r at row r, record g.  The host allocates the rows in chunks
+// as the rounds go by and hands k_arena_move the row of its round; the records of games that are not alive are never written.
+struct ArenaTurn {
+    int8_t play[4];         // all kNoMove: a skipped turn
+    uint8_t roll[2];        // the state's roll before the move
+    uint8_t next_roll[2];   // the dice apply_move / skip_turn was given
+    int8_t player;          // the state's side to move, -1 / +1
+    uint8_t agent;          // DIEE_AGENT_* of the player that moved
+    uint8_t second;         // is_second_play before the move
+    uint8_t retired;        // the turn retired the game
+};
+static_assert(sizeof(ArenaTurn) == 12, "diee_turn is 12 bytes");
 struct ArenaParams {
     unsigned long long seed;
     uint32_t round, round_limit;
     float inv_temperature;
     uint32_t side;          // 0: player 1's list, 1: player 2's
     uint32_t agent;         // DIEE_AGENT_RANDOM / DIEE_AGENT_MODEL / DIEE_AGENT_MCTS of that player
+    ArenaTurn* log;         // [n_games] this round's row of the turn log; null: no log
 };
 
 // ---- Agent::Mcts (diee_mcts_vanilla_batch; simple_mcts.rs:10-39, node.rs) ---------------------------------------------------------

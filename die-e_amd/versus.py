@@ -7,6 +7,11 @@ Q22); DIEE_VANILLA_ROLLOUTS=1 (or vanilla_rollouts=True) turns the quirk off -- 
 `play` is written against a small backend interface so that the same driver can run on the engine or,
 in the parity tests, on the CPU oracle.  `play_device` is the same arena as ONE engine call (diee_arena): every round
 on the device, the same games bit for bit (Model, Mcts and Random agents); DIEE_ARENA=device makes the callers use it.
+
+The reference declares Turn { roll, action, player } and Game.turns, and print_game walks them, but play() never pushes one (Q21).
+record_turns=True (DIEE_RECORD_TURNS=1 for `diee.py play`) is the replay as it was meant -- opt-in and logged: both drivers record
+every turn with the two fields that make it replayable (next_roll, is_second_play), replay_states re-plays and audits a recorded
+game, print_game shows the board after each turn.
 """
 import json
 import os
@@ -81,6 +86,23 @@ def vanilla_rollouts_from_env(log=None):
         (log or (lambda m: sys.stderr.write(m + "\n")))("[diee] DIEE_VANILLA_ROLLOUTS=1: Agent::Mcts plays its rollouts "
                                                         "(deviation from the reference, whose simulate() returns 0: Q22)")
     return on
+
+
+def record_turns_from_env(log=None):
+    """DIEE_RECORD_TURNS=1: saved games carry their turns (the reference never fills Game.turns: Q21), opt-in and logged"""
+    on = os.environ.get("DIEE_RECORD_TURNS") == "1"
+    if on:
+        (log or (lambda m: sys.stderr.write(m + "\n")))("[diee] DIEE_RECORD_TURNS=1: games are saved with their turns, each with next_roll and "
+                                                        "is_second_play (deviation from the reference, whose play() pushes no turn: Q21)")
+    return on
+
+
+def turn_json(roll, play, player, next_roll, second):
+    """Turn { roll, action, player } (versus.rs:21-26) as JSON, plus what makes it replayable: action = the (from, to) pairs of the play,
+    none for a skipped turn; player = the Agent that moved; next_roll = the dice apply_move / skip_turn was given"""
+    p = [int(x) for x in play]
+    return {"roll": [int(roll[0]), int(roll[1])], "action": [[p[i], p[i + 1]] for i in (0, 2) if p[i] != NO_MOVE], "player": player,
+            "next_roll": [int(next_roll[0]), int(next_roll[1])], "is_second_play": bool(second)}
 
 
 def new_states(n):
@@ -171,6 +193,96 @@ def to_pretty_str(st):                         # backgammon_logic.rs:110-174
     return f"{info}\n{bar}\n{body}\n{bar}"
 
 
+def state_from_json(st):
+    """Game.initial_state -> one BG_STATE record"""
+    s = np.zeros(1, dtype=BG_STATE)
+    s["pts"][0], s["bar"][0], s["off"][0] = st["board"][0], st["board"][1], st["board"][2]
+    s["roll"][0], s["player"][0], s["second"][0] = st["roll"], st["player"], 1 if st["is_second_play"] else 0
+    return s[0]
+
+
+def apply_turn(st, turn):
+    """the state (a dict like Game.initial_state) after a recorded turn, on the host: apply_move (backgammon_logic.rs:176-186, its moves by
+    get_next_state, :467-517) or skip_turn (:192-196) with the turn's next_roll.  What print_game needs; nothing is checked here
+    (replay_states checks a game against the rules)"""
+    pts, bar, off = (list(x) for x in st["board"])
+    player = st["player"]
+    me = 0 if player < 0 else 1
+    for f, t in turn["action"]:
+        if t == -1:                            # collect
+            pts[f] -= player; off[me] += 1
+            continue
+        hit = pts[t] == -player
+        if f == -1:                            # from the bar
+            bar[me] -= 1
+        else:
+            pts[f] -= player
+        if hit:
+            pts[t] += 2 * player; bar[1 - me] += 1
+        else:
+            pts[t] += player
+    out = dict(st, board=[pts, bar, off])
+    if turn["action"] and st["roll"][0] == st["roll"][1] and not st["is_second_play"]:
+        out["is_second_play"] = True           # the second half of a double: same side, same roll
+    else:
+        out.update(roll=list(turn["next_roll"]), player=-player, is_second_play=False)
+    return out
+
+
+def replay_all(games, rules):
+    """replay_states for several games at once (one rules call per turn index for all of them)"""
+    docs = [g.to_json() if isinstance(g, Game) else g for g in games]
+    cur = np.array([state_from_json(d["initial_state"]) for d in docs], dtype=BG_STATE).reshape(len(docs))
+    outs = [np.zeros(len(d["turns"]), dtype=BG_STATE) for d in docs]
+    for t in range(max([len(d["turns"]) for d in docs], default=0)):
+        act = np.array([i for i, d in enumerate(docs) if t < len(d["turns"])])
+        sub = cur[act]
+        vm, cnt = rules.valid_moves(sub)
+        plays = np.full((len(act), 4), NO_MOVE, dtype=np.int8)
+        dice = np.zeros((len(act), 2), dtype=np.uint8)
+        for k, i in enumerate(act):
+            d, turn = docs[i], docs[i]["turns"][t]
+            where = f"game {d['initial_state']['id']} ({d['id']}), turn {t}: "
+            if "next_roll" not in turn:
+                raise ValueError(where + "the record has no next_roll (not recorded by this project: nothing to replay)")
+            if [int(x) for x in sub[k]["roll"]] != list(turn["roll"]):
+                raise ValueError(where + f"recorded roll {turn['roll']}, the state's is {[int(x) for x in sub[k]['roll']]}")
+            if bool(sub[k]["second"]) != bool(turn["is_second_play"]):
+                raise ValueError(where + f"recorded is_second_play {turn['is_second_play']}, the state's is {bool(sub[k]['second'])}")
+            mover = d["player1"] if sub[k]["player"] == -1 else d["player2"]
+            if turn["player"] != mover:
+                raise ValueError(where + f"recorded player {turn['player']}, to move is {mover}")
+            flat = [x for pair in turn["action"] for x in pair]
+            if not flat:
+                if mover in (Agent.RANDOM, Agent.MCTS) and cnt[k] != 0:
+                    raise ValueError(where + f"a skipped turn of a {mover} agent with {int(cnt[k])} legal plays")
+            else:
+                if len(flat) not in (2, 4):
+                    raise ValueError(where + f"action {turn['action']} is not one or two (from, to) pairs")
+                plays[k, :len(flat)] = flat
+                if not (vm[k][:cnt[k]] == plays[k]).all(axis=1).any():
+                    raise ValueError(where + f"action {turn['action']} is not a valid move")
+            dice[k] = turn["next_roll"]
+        empty = plays[:, 0] == NO_MOVE
+        new = sub.copy()
+        if empty.any():
+            new[empty] = skip_turn(sub[empty], dice[empty])
+        if (~empty).any():
+            new[~empty] = rules.apply(sub[~empty], plays[~empty], dice[~empty])
+        cur[act] = new
+        for k, i in enumerate(act):
+            outs[i][t] = new[k]
+    return outs
+
+
+def replay_states(game, rules):
+    """the state after every turn of a recorded game (a Game or its JSON), by rules.apply / skip_turn with the recorded dice -> BG_STATE
+    [len(turns)].  Audits the record on the way: every turn's roll, is_second_play and player against the state, every action against
+    rules.valid_moves, and that a Random or Mcts agent skipped only without a legal play; ValueError on the first mismatch, naming the
+    game and the turn"""
+    return replay_all([game], rules)[0]
+
+
 def print_game(path, wait_user_input=False, out=print):     # versus.rs:75-105
     g = load_game(path)
     out(f"Game ID: {g['id']}")
@@ -178,9 +290,12 @@ def print_game(path, wait_user_input=False, out=print):     # versus.rs:75-105
     out(f"Game winner: {g['winner']}")
     out("Initial State:")
     out(to_pretty_str(g["initial_state"]))
+    state = g["initial_state"]
     for turn in g["turns"]:
         out(f"Player: {turn['player']}"); out(f"Roll: {turn['roll']}"); out(f"Action: {turn['action']}")
-        out("State after action has been played:"); out(to_pretty_str(g["initial_state"]))
+        if "next_roll" in turn:                # a turn this project recorded: the two lines versus.rs:92-93 comment out
+            state = apply_turn(state, turn)
+        out("State after action has been played:"); out(to_pretty_str(state))
         if wait_user_input:
             input("Press Enter to continue...")
 
@@ -235,11 +350,12 @@ def get_actions_for_player(player, states, ids, rnd, mcts_config, temp, seed, ru
 
 
 def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, rules=None,
-         search1=None, search2=None, max_rounds=0, vanilla_rollouts=None):
+         search1=None, search2=None, max_rounds=0, vanilla_rollouts=None, record_turns=False):
     """play(), versus.rs:160-268.  player1 plays side -1 in every game; the second half of the games starts
     with side +1 to move (:172-174).  max_rounds > 0 stops the loop after that many rounds (the games still alive
     are not in `games`); 0 plays to the end.  An Mcts player searches on its engine (Player.model) or on search1 / search2;
-    vanilla_rollouts: its rollouts are played (Q22 off); None reads DIEE_VANILLA_ROLLOUTS."""
+    vanilla_rollouts: its rollouts are played (Q22 off); None reads DIEE_VANILLA_ROLLOUTS.  record_turns: every Game's `turns` is filled (Q21)
+    and PlayResult.turns holds them for every game index, retired or not."""
     if vanilla_rollouts is None:
         vanilla_rollouts = Agent.MCTS in (player1.player_type, player2.player_type) and vanilla_rollouts_from_env()
     if rules is None:
@@ -284,6 +400,10 @@ def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, ro
                        axis=1).astype(np.uint32)
         dice, _ = rules.draws(seed, ctr)
         pl = np.stack([acts[int(g)] for g in order])
+        if record_turns:                       # the turn as it is about to be played: the state's roll, the action, who moves, the dice it is given
+            for k, g in enumerate(order):
+                mover = player1.player_type if k < len(p1) else player2.player_type
+                games[g].turns.append(turn_json(states[g]["roll"], pl[k], mover, dice[k], states[g]["second"]))
         empty = pl[:, 0] == NO_MOVE
         if empty.any():                        # :225-228 skip_turn; continue (no winner / round-limit check)
             states[order[empty]] = skip_turn(states[order[empty]], dice[empty])
@@ -310,6 +430,7 @@ def play(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, ro
     res = PlayResult(player1.player_type, player2.player_type, wins_p1, wins_p2, num_games, played)
     res.final_states = states
     res.rounds = round_count
+    res.turns = [g.turns for g in games] if record_turns else None
     return res
 
 
@@ -334,27 +455,40 @@ def games_from_device(player1, player2, initial_states, winner, retired_round, r
 
 
 def play_device(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, max_rounds=0, engine=None,
-                vanilla_rollouts=None):
+                vanilla_rollouts=None, record_turns=False):
     """play() with every round on the device (Engine.arena, diee_arena): the same PlayResult -- wins, draws, rounds, final_states,
     games in play()'s order -- from one engine call.  Model, Mcts and Random agents; `engine` hosts a call none of whose players brings an
-    engine.  vanilla_rollouts as in play(): ONE flag word governs both players' searches of a diee_arena call, so an Mcts agent with played
-    rollouts against a Model agent (which play() searches with the quirks on) is the host driver's to run."""
-    from . import AGENT_MCTS, AGENT_MODEL, AGENT_RANDOM, arena
+    engine.  vanilla_rollouts as in play(): the Mcts agent's searches run without the quirks, a Model agent's with them (a flag word per
+    player, diee_arena_ex).  record_turns: Game.turns and PlayResult.turns from the device's turn log, the same turns play() records."""
+    from . import AGENT_MCTS, AGENT_MODEL, AGENT_RANDOM, FLAG_REF_QUIRKS, arena
     kinds = {Agent.MODEL: AGENT_MODEL, Agent.RANDOM: AGENT_RANDOM, Agent.MCTS: AGENT_MCTS}
     types = (player1.player_type, player2.player_type)
     if vanilla_rollouts is None:
         vanilla_rollouts = Agent.MCTS in types and vanilla_rollouts_from_env()
-    if vanilla_rollouts and Agent.MODEL in types:
-        raise ValueError("Mcts with played rollouts against a Model agent: use play() (diee_arena has one quirks flag for both searches)")
+    # the quirks per player, as play() searches: a Model agent always with them, an Mcts agent without them when its rollouts are played
+    quirks = [not (vanilla_rollouts and t == Agent.MCTS) for t in types]
+    for s in (0, 1):
+        if types[s] == Agent.RANDOM:           # (a Random agent searches nothing: the other player's word)
+            quirks[s] = quirks[1 - s]
     e1, e2 = player1.model, player2.model
     if e1 is None and e2 is None:
         e1 = engine                            # no player brings an engine (Random, Mcts): any engine hosts the call
     r = arena(e1, kinds[player1.player_type], e2, kinds[player2.player_type], num_games, mcts_config, temp, seed, round_limit, max_rounds,
-              ref_quirks=not vanilla_rollouts)
+              ref_quirks=quirks[0], record_turns=record_turns,
+              flags2=None if quirks[0] == quirks[1] else (FLAG_REF_QUIRKS if quirks[1] else 0))
     games = games_from_device(player1, player2, r["initial_states"], r["winner"], r["retired_round"], r["retired_side"])
+    turns = None
+    if record_turns:
+        names = {v: k for k, v in kinds.items()}
+        rec, first = r["turns"], r["first"].tolist()
+        roll, pl, agent, nxt, second = (rec[k].tolist() for k in ("roll", "play", "agent", "next_roll", "second"))     # (Python ints: the lists are long)
+        turns = [[turn_json(roll[i], pl[i], names[agent[i]], nxt[i], second[i]) for i in range(first[g], first[g + 1])] for g in range(num_games)]
+        for game in games:
+            game.turns = turns[game.initial_state["id"]]
     res = PlayResult(player1.player_type, player2.player_type, r["wins_p1"], r["wins_p2"], num_games, games)
     res.final_states = r["final_states"]
     res.rounds = r["rounds"]
+    res.turns = turns
     res.device = r                             # the call's per-game outputs and per-player stats
     return res
 

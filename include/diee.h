@@ -198,6 +198,10 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *   vanilla_iters_per_launch   Agent::Mcts (diee_mcts_vanilla_batch, DIEE_AGENT_MCTS): iterations a game runs in one launch at most; the trees stay
  *                                 in HBM from launch to launch and the results do not depend on it.  Default 0: derived from the call's
  *                                 round_limit so that a launch stays far below a second (16384 / (round_limit + 1); 4096 under DIEE_FLAG_REF_QUIRKS)
+ *   arena_log_rounds      diee_arena_ex with a turn log: rounds per chunk of the log's device rows (n_games x 12 bytes per round; default 64;
+ *                                 a chunk is cut short where arena_log_mb would not hold a whole one).  The log does not depend on it
+ *   arena_log_mb          MiB of HBM the turn log of one diee_arena_ex call may take (default 1024): a round that needs another row
+ *                                 beyond it is not played, the call returns DIEE_ERR_CAPACITY
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
  *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
  *                                 diee_self_play_refill of this ctx allocated: min(width, games of the call), whatever the call's length
@@ -355,7 +359,8 @@ diee_status diee_self_play_refill(diee_ctx*, const diee_batch* batches, uint32_t
  * it borrows p2's network -- weights, activations, dispatch tables -- and touches nothing else of p2.  p2 on another device: DIEE_ERR_ARG;
  * p2 == p1 is allowed; the ctx of a Random agent may be NULL as long as the other one is not (then that one hosts the call).  A Model agent
  * whose ctx is NULL: DIEE_ERR_ARG, without loaded weights: DIEE_ERR_NO_WEIGHTS; a tic-tac-toe ctx: DIEE_ERR_UNSUPPORTED; n_games == 0 or
- * round_limit == 0: DIEE_ERR_ARG.  flags: DIEE_FLAG_REF_QUIRKS (what a driver over diee_mcts_batch searches with), DIEE_FLAG_INVARIANT_NN.
+ * round_limit == 0: DIEE_ERR_ARG.  flags: DIEE_FLAG_REF_QUIRKS (what a driver over diee_mcts_batch searches with), DIEE_FLAG_INVARIANT_NN --
+ * one word for both players' searches here; diee_arena_ex below takes one per player.
  * max_rounds = 0 plays to the end; otherwise the call stops after that many rounds and the live games keep winner 0, retired_round UINT32_MAX
  * (retired_side -1).  The host synchronises with the device once per round (three words: the two sides' counts and the games alive) on top
  * of what the searches do.
@@ -385,6 +390,55 @@ diee_status diee_arena(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2,
                        diee_bg_state* initial_states /* [n_games] or NULL */,
                        diee_bg_state* final_states   /* [n_games] or NULL */,
                        diee_stats* stats /* [2], per player, or NULL */);
+
+/* ---- the arena with options: a flag word per player and the turn log.  diee_arena(..., flags, ...) is this call with
+ * flags[0] == flags[1] == flags and no log; every other argument, output and rule is diee_arena's.
+ *   flags[s] governs player s's searches (s = 0: player 1): DIEE_FLAG_REF_QUIRKS for its diee_mcts_batch or vanilla search,
+ *   DIEE_FLAG_INVARIANT_NN for its network -- e.g. an Mcts agent with played rollouts (no quirks) against a Model agent searched as a
+ *   host-side driver over diee_mcts_batch searches it (quirks).
+ *   log != NULL: every turn of every game is recorded -- Turn { roll, action, player }, versus.rs:21-26, which the reference declares,
+ *   walks in print_game (:88-95) and never fills.  A record:
+ *     play       the action, a diee_bg_legal_moves play; all DIEE_NO_MOVE = the turn was skipped (skip_turn, :225-228)
+ *     roll       the state's roll before the move (Turn.roll)
+ *     player     the state's side to move, -1 / +1; agent = DIEE_AGENT_* of the player that moved (Turn.player)
+ *     next_roll  the dice apply_move / skip_turn was given, (seed, game, round, TAG_MOVE_ROLL); second = is_second_play before the move.
+ *                These two are the engine's additions: with them a turn is replayable from the state before it (diee_bg_apply with
+ *                next_roll, or skip_turn: second = 0, player = -player, roll = next_roll), and turn t + 1's roll is turn t's next_roll
+ *                unless turn t was the first half of a double
+ *     retired    1 on the turn that retired the game (a winner, or the round limit), so on at most the last record of a game
+ *   Game g's turns are turns[first[g] .. first[g + 1]) in play order: retired_round[g] + 1 of them, or the rounds of the call for a game
+ *   still alive when max_rounds stopped it.  The engine owns the log until diee_free_arena_log (a log the call did not fill is zeroed:
+ *   freeing it is harmless).  On the device the log is round-major rows of n_games records (a live game takes exactly one turn per
+ *   round), allocated option arena_log_rounds rounds at a time as the call goes on; their total is bounded by option arena_log_mb, and a
+ *   round whose row would exceed it is not played: DIEE_ERR_CAPACITY, never a truncated log.
+ * opts == NULL or opts->struct_size != sizeof(diee_arena_opts): DIEE_ERR_ARG.  A tic-tac-toe ctx: DIEE_ERR_UNSUPPORTED. */
+typedef struct {
+    int8_t  play[4];
+    uint8_t roll[2];
+    uint8_t next_roll[2];
+    int8_t  player;
+    uint8_t agent;
+    uint8_t second;
+    uint8_t retired;
+} diee_turn;                   /* 12 bytes */
+typedef struct {
+    diee_turn* turns;          /* [first[n_games]]                                          */
+    uint64_t*  first;          /* [n_games + 1]                                             */
+    uint32_t   n_games;
+    void*      owner;          /* the engine's: what diee_free_arena_log releases           */
+} diee_arena_log;
+typedef struct {
+    uint32_t struct_size;      /* sizeof(diee_arena_opts)                                   */
+    uint32_t flags[2];         /* per player                                                */
+    diee_arena_log* log;       /* NULL: no turn log                                         */
+} diee_arena_opts;
+
+diee_status diee_arena_ex(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2,
+                          uint32_t n_games, const diee_mcts_cfg* cfg, float temperature,
+                          uint64_t seed, uint32_t round_limit, uint32_t max_rounds, const diee_arena_opts* opts,
+                          diee_arena_result* res, int8_t* winner, uint32_t* retired_round, int8_t* retired_side,
+                          diee_bg_state* initial_states, diee_bg_state* final_states, diee_stats* stats);
+void        diee_free_arena_log(diee_arena_log* log);
 
 /* ---- training-step kernels (no ctx: plain device pointers of the caller's framework, launched on `stream`, a
  * hipStream_t; NULL = the default stream).  AlphaZero::train (alphazero.rs:202-261) is tch autograd in the reference;

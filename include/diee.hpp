@@ -78,6 +78,8 @@ public:
         }
         return out;
     }
+    // apply_move, backgammon_logic.rs:176-186, with the dice roll_die would draw
+    Backgammon apply_move(Backgammon s, const Play& p, const uint8_t dice[2]) { chk(diee_bg_apply(ctx_, &s, p.mv, dice, 1)); return s; }
     uint32_t encode(const Backgammon& s, const Play& p) { uint32_t c = 0; chk(diee_bg_encode(ctx_, &s, p.mv, 1, &c)); return c; }
     Play decode(const Backgammon& s, uint32_t code) { Play p; chk(diee_bg_decode(ctx_, &s, &code, 1, p.mv)); return p; }
     std::vector<float> as_tensor(const Backgammon& s) { std::vector<float> t(DIEE_BG_PLANES); chk(diee_bg_planes(ctx_, &s, 1, t.data())); return t; }
@@ -159,15 +161,33 @@ public:
         std::vector<uint32_t> retired_round;                     // UINT32_MAX: still alive (max_rounds)
         std::vector<Backgammon> initial_states, final_states;
         diee_stats stats[2];
+        // record_turns: Game.turns (versus.rs:21-35) of every game -- game g's are turns[first[g] .. first[g + 1]) in play order; each replayable
+        // with diee_bg_apply and its next_roll (include/diee.h, diee_turn)
+        std::vector<diee_turn> turns;
+        std::vector<uint64_t> first;
     };
+    // ref_quirks2: the quirks of player 2's searches where they differ from player 1's (-1: the same), e.g. an Mcts agent with played rollouts
+    // (false) against a Model agent (true)
     ArenaResult arena(Engine* player2, const MctsConfig& cfg, float temperature, uint64_t seed, uint32_t num_games = 400, uint32_t round_limit = 400,
-                      int agent1 = DIEE_AGENT_MODEL, int agent2 = DIEE_AGENT_MODEL, uint32_t max_rounds = 0, bool ref_quirks = true) {
+                      int agent1 = DIEE_AGENT_MODEL, int agent2 = DIEE_AGENT_MODEL, uint32_t max_rounds = 0, bool ref_quirks = true,
+                      bool record_turns = false, int ref_quirks2 = -1) {
         ArenaResult r;
         r.winner.resize(num_games); r.retired_side.resize(num_games); r.retired_round.resize(num_games);
         r.initial_states.resize(num_games); r.final_states.resize(num_games);
-        chk(diee_arena(ctx_, agent1, player2 ? player2->ctx_ : nullptr, agent2, num_games, &cfg, temperature, seed, round_limit, max_rounds,
-                       ref_quirks ? DIEE_FLAG_REF_QUIRKS : 0u, &r.result, r.winner.data(), r.retired_round.data(), r.retired_side.data(),
-                       r.initial_states.data(), r.final_states.data(), r.stats));
+        diee_arena_log log = {nullptr, nullptr, 0, nullptr};
+        diee_arena_opts opts;
+        opts.struct_size = (uint32_t)sizeof opts;
+        opts.flags[0] = ref_quirks ? DIEE_FLAG_REF_QUIRKS : 0u;
+        opts.flags[1] = ref_quirks2 < 0 ? opts.flags[0] : ref_quirks2 ? DIEE_FLAG_REF_QUIRKS : 0u;
+        opts.log = record_turns ? &log : nullptr;
+        chk(diee_arena_ex(ctx_, agent1, player2 ? player2->ctx_ : nullptr, agent2, num_games, &cfg, temperature, seed, round_limit, max_rounds,
+                          &opts, &r.result, r.winner.data(), r.retired_round.data(), r.retired_side.data(),
+                          r.initial_states.data(), r.final_states.data(), r.stats));
+        if (record_turns) {
+            r.first.assign(log.first, log.first + num_games + 1);
+            r.turns.assign(log.turns, log.turns + r.first[num_games]);
+            diee_free_arena_log(&log);
+        }
         if (r.result.illegal_decodes) throw Error(DIEE_ERR_CAPACITY, "decoded action is not a valid move (versus.rs:229)");
         return r;
     }
