@@ -39,7 +39,8 @@ OK, ERR_ARG, ERR_HIP, ERR_NO_WEIGHTS, ERR_CAPACITY, ERR_UNSUPPORTED = range(6)
 BG_STATE = np.dtype([("pts", "i1", 24), ("bar", "u1", 2), ("off", "u1", 2), ("roll", "u1", 2),
                      ("player", "i1"), ("second", "u1")])
 assert BG_STATE.itemsize == 32
-# tic-tac-toe (BASELINE configs[0]): diee_ttt_state; an Engine(game_id=GAME_TTT) runs on the host (csrc/ttt_host.cpp)
+# tic-tac-toe (BASELINE configs[0]): diee_ttt_state; an Engine(game_id=GAME_TTT) runs on the host (csrc/ttt_host.cpp), its network on the
+# GPU after set_option("nn", "device") (csrc/ttt_kernels.hip)
 TTT_ACTIONS, TTT_PLANES = 9, 27
 TTT_STATE = np.dtype([("board", "i1", 9), ("player", "i1"), ("pad", "u1", 22)])
 assert TTT_STATE.itemsize == 32
@@ -328,6 +329,9 @@ class Engine:
     # ---- options of the ctx (diee_set_option: what used to be DIEE_* environment switches) ----
     def set_option(self, key, value):
         """e.g. set_option("shared_gpu", 1) when several processes compute on this GPU; include/diee.h lists the keys"""
+        if self.game_id == GAME_TTT and _TORCH_LOADED_FIRST and (key, value) == ("nn", "device"):
+            import sys
+            sys.modules["torch"].cuda.is_available()      # the tic-tac-toe ctx touches the GPU here for the first time (see __init__)
         self._chk(self._L.diee_set_option(self._h, str(key).encode(), str(value).encode()))
         return self
 

@@ -69,7 +69,7 @@ def get_all_paths_rec(d, res):
 
 def main_tictactoe(args):
     """handle_command::<TicTacToe> (main.rs:112-114,119-216): the same driver on the tic-tac-toe host engine (BASELINE
-    configs[0]: CPU path, no GPU): learn, train and play; nothing here touches the HIP engine"""
+    configs[0]: CPU path, no GPU): learn, train and play; nothing here touches the HIP engine unless DIEE_TTT_NN=device asks for it"""
     from . import GAME_TTT, Engine
     from .alphazero import TICTACTOE, AlphaZero, load_config, mcts_config_from
     from .versus import Agent, Player, play_tictactoe
@@ -77,7 +77,14 @@ def main_tictactoe(args):
     if args.command == "replay":
         sys.exit("replay prints backgammon boards (versus.rs:75-105 over Game<Backgammon> files)")
     conf = load_config(args.config)
-    eng = Engine(0, GAME_TTT)
+
+    def engine():
+        e = Engine(0, GAME_TTT)
+        if os.environ.get("DIEE_TTT_NN") == "device":                                         # opt-in: the network on the GPU (k_ttt_net), the search on the host
+            e.set_option("nn", "device")
+            print("[die-e_amd] DIEE_TTT_NN=device: the tic-tac-toe network is evaluated on GPU 0 (bf16 MFMA); the search stays on the host")
+        return e
+    eng = engine()
     if args.command == "learn":
         az = AlphaZero.from_config(eng, conf, model_path=args.model_path, game=TICTACTOE, train_device="cpu")
         for row in az.learn_parallel():
@@ -98,7 +105,7 @@ def main_tictactoe(args):
         def model(path):
             if path is None:
                 return None
-            e = Engine(0, GAME_TTT); e.load_weights(load_model(path)); return e
+            e = engine(); e.load_weights(load_model(path)); return e
         a1, a2 = Agent.parse(args.agent_one), Agent.parse(args.agent_two)
         print(play_tictactoe(Player(a1, model(args.model_path_one)), Player(a2, model(args.model_path_two)), mcts_config_from(conf),
                              float(conf["temperature"])))

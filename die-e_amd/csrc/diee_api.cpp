@@ -67,7 +67,7 @@ diee_status diee_create(int device, int game_id, diee_ctx** out) {
         c = new diee_ctx();
         c->err[0] = 0; c->game = game_id;
         if (game_id == DIEE_GAME_TTT) {
-            c->ttt = new ttt::Engine();                 // BASELINE configs[0]: host path, no GPU involved (`device` is not looked at)
+            c->ttt = new ttt::Engine(device);           // BASELINE configs[0]: host path; `device` is kept for option "nn" = "device", no HIP call before
         } else {
             int ndev = 0;
             if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { delete c; return DIEE_ERR_HIP; }
@@ -97,14 +97,15 @@ diee_status diee_device_pci_bus_id(int device, char* out, size_t cap) {
 diee_status diee_set_option(diee_ctx* c, const char* key, const char* value) {
     API_BEGIN(c)
     if (!key || !value) throw EngineError(DIEE_ERR_ARG, "null pointer");
-    bg(c)->set_option(key, value);
+    if (c->ttt) c->ttt->set_option(key, value);
+    else bg(c)->set_option(key, value);
     API_END(c)
 }
 
 diee_status diee_get_option(diee_ctx* c, const char* key, char* value, size_t cap) {
     API_BEGIN(c)
     if (!key || !value || !cap) throw EngineError(DIEE_ERR_ARG, "null pointer");
-    const std::string v = bg(c)->get_option(key);
+    const std::string v = c->ttt ? c->ttt->get_option(key) : bg(c)->get_option(key);
     if (v.size() + 1 > cap) throw EngineError(DIEE_ERR_ARG, "value buffer too small");
     memcpy(value, v.c_str(), v.size() + 1);
     API_END(c)

@@ -15,6 +15,7 @@
 #include "bg_device.h"
 #include "engine.h"
 #include "search_host.h"
+#include "ttt_device.h"
 
 namespace diee {
 namespace ttt {
@@ -95,6 +96,24 @@ void random_weights(uint64_t seed, float* blob) {
     { const float bd = 1.0f / std::sqrt((float)(VH * HW)); uni(L.vfw, (size_t)VH * HW, -bd, bd); uni(L.vfb, 1, -bd, bd); }
 }
 
+Engine::Engine(int device) : device_(device) {}
+Engine::~Engine() = default;
+
+void Engine::set_option(const std::string& key, const std::string& value) {
+    if (key != "nn") throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has one option, `nn`; `" + key + "` belongs to a backgammon ctx");
+    if (value == "host") { dev_.reset(); return; }
+    if (value != "device") throw EngineError(DIEE_ERR_ARG, "option nn: `" + value + "` is neither `host` nor `device`");
+    if (dev_) return;
+    std::unique_ptr<DeviceNet> d(new DeviceNet(device_));                // throws DIEE_ERR_HIP without a usable GPU: dev_ stays empty
+    dev_ = std::move(d);
+    try { if (loaded()) upload(); } catch (...) { dev_.reset(); throw; }
+}
+std::string Engine::get_option(const std::string& key) const {
+    if (key != "nn") throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has one option, `nn`; `" + key + "` belongs to a backgammon ctx");
+    return dev_ ? "device" : "host";
+}
+void Engine::upload() const { dev_->upload(init_, c1_, c2_, pconv_, vconv_, pfc_w_, pfc_b_, vfc_w_, vfc_b_); }
+
 void Engine::load_weights(const float* blob, size_t n) {
     const Layout& L = layout();
     if (n != L.total) throw EngineError(DIEE_ERR_ARG, "weight blob has " + std::to_string(n) + " floats, expected " + std::to_string(L.total));
@@ -113,6 +132,9 @@ void Engine::load_weights(const float* blob, size_t n) {
     pfc_w_.assign(blob + L.pfw, blob + L.pfw + (size_t)A * PH * HW); pfc_b_.assign(blob + L.pfb, blob + L.pfb + A);
     vfc_w_.assign(blob + L.vfw, blob + L.vfw + (size_t)VH * HW); vfc_b_.assign(blob + L.vfb, blob + L.vfb + 1);
     w_.assign(blob, blob + n);
+    // a failed upload must not leave "device" answering with the previous network: the ctx falls back to "host" (which holds the new
+    // weights) and the caller gets the HIP error, as in set_option
+    if (dev_) { try { upload(); } catch (...) { dev_.reset(); throw; } }
 }
 
 // ---- the network, fp32 ------------------------------------------------------------------------------------------------
@@ -148,6 +170,7 @@ inline void relu(float* x, int n) { for (int i = 0; i < n; ++i) x[i] = x[i] > 0.
 
 void Engine::forward(const diee_ttt_state* s, uint32_t n, float* policy, float* value) const {
     if (!loaded()) throw EngineError(DIEE_ERR_NO_WEIGHTS, "diee_load_weights has not been called");
+    if (dev_) { dev_->forward(s, n, policy, value); return; }
     std::vector<float> x(F * 9), h(F * 9), t(F * 9), in(PLANES), ph(PH * 9), vh(VH * 9);
     for (uint32_t i = 0; i < n; ++i) {
         planes(s[i], in.data());

@@ -8,10 +8,14 @@
 // 28-100), the fp32 ResNet (src/alphazero/nnet.rs:24-34,57-133 with N_FILTERS = 64, N_RES_BLOCKS = 4, mod.rs:20-24),
 // the batched search (src/mcts/alpha_mcts.rs:91-202) and the self-play driver (src/alphazero/alpha_parallel.rs:101-231).
 // It is reached only through diee_create(.., DIEE_GAME_TTT, ..); the backgammon path has no host fallback.
+// At the reference's batch sizes (1024 games per search) the network IS work for the chip: option "nn" = "device" (opt-in) sends
+// forward() to one launch of k_ttt_net (ttt_device.h); rules, search and driver stay here.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include <memory>
+#include <string>
 #include <vector>
 
 #include "../../include/diee.h"
@@ -31,11 +35,22 @@ void planes(const diee_ttt_state& s, float out[27]);              // :83-94
 size_t weights_count();
 void random_weights(uint64_t seed, float* blob);
 
+struct Conv { std::vector<float> w, b; int cout = 0, cin = 0; };          // OIHW, BatchNorm folded (eval mode, eps 1e-5)
+class DeviceNet;                                                          // ttt_device.h
+
 class Engine {
 public:
+    explicit Engine(int device = 0);                                      // `device`: the GPU option "nn" = "device" would use; not touched before
+    ~Engine();
+    // option "nn" (include/diee.h): "host" (default) = the fp32 loops below, "device" = k_ttt_net (ttt_device.h) behind forward().
+    // Every other key: DIEE_ERR_UNSUPPORTED.  A failed switch to "device" (no usable GPU: DIEE_ERR_HIP) leaves the ctx on the host path.
+    void set_option(const std::string& key, const std::string& value);
+    std::string get_option(const std::string& key) const;
     void load_weights(const float* blob, size_t n);
     bool loaded() const { return !w_.empty(); }
-    // ResNet::forward_t (nnet.rs:120-133), eval mode: softmax policy [n][9], tanh value [n]
+    // ResNet::forward_t (nnet.rs:120-133), eval mode: softmax policy [n][9], tanh value [n].  `const` as the searches below call it; on
+    // the host path it is re-entrant, on the device path it is NOT: it goes through the ctx's one stream and staging buffers (one call
+    // at a time per ctx, like every entry point of a backgammon ctx) and leaves the calling thread's current HIP device set to the ctx's.
     void forward(const diee_ttt_state* s, uint32_t n, float* policy, float* value) const;
     void mcts_batch(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step,
                     const uint32_t* game_ids, const uint32_t* rounds, uint32_t flags, float* visit_probs, uint32_t* n_children,
@@ -44,7 +59,9 @@ public:
                    uint32_t flags, uint32_t max_steps, diee_fragments* out, diee_stats* stats) const;
 
 private:
-    struct Conv { std::vector<float> w, b; int cout = 0, cin = 0; };      // BatchNorm folded (eval mode, eps 1e-5)
+    void upload() const;                                                    // the folded weights -> dev_
+    int device_;
+    std::unique_ptr<DeviceNet> dev_;                                        // non-null = "nn" is "device"
     Conv init_, c1_[BLOCKS], c2_[BLOCKS], pconv_, vconv_;
     std::vector<float> pfc_w_, pfc_b_, vfc_w_, vfc_b_;
     std::vector<float> w_;                                                  // the blob as loaded (non-empty = loaded)

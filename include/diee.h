@@ -65,8 +65,8 @@ typedef struct {
  * a ctx created with DIEE_GAME_TTT runs rules, the 64-filter 4-block ResNet (mod.rs:20-24), the search and the
  * self-play driver in C++ on the HOST (die-e_amd/csrc/ttt_host.cpp) and needs no GPU; its states are diee_ttt_state
  * records (cast the pointer where a prototype says diee_bg_state), policies / ps rows have 9 entries, planes 27.
- * Served for such a ctx: diee_load_weights, diee_nn_forward, diee_mcts_batch, diee_self_play (+ lifetime / error calls);
- * everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no host path. */
+ * Served for such a ctx: diee_load_weights, diee_nn_forward, diee_mcts_batch, diee_self_play (+ lifetime / error calls) and the
+ * one option "nn" (below); everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no host path. */
 typedef struct {
     int8_t  board[9];          /* 0 | 1 | 2 / 3 | 4 | 5 / 6 | 7 | 8; -1 / 0 / +1            */
     int8_t  player;            /* -1 moves first, mod.rs:28-30                              */
@@ -202,6 +202,14 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *                                 a chunk is cut short where arena_log_mb would not hold a whole one).  The log does not depend on it
  *   arena_log_mb          MiB of HBM the turn log of one diee_arena_ex call may take (default 1024): a round that needs another row
  *                                 beyond it is not played, the call returns DIEE_ERR_CAPACITY
+ *   nn                    "host" | "device"   TIC-TAC-TOE ctx only, and its only option (a backgammon ctx: DIEE_ERR_ARG, unknown option; any other
+ *                                 key on a tic-tac-toe ctx: DIEE_ERR_UNSUPPORTED).  "device": diee_nn_forward and the network evaluations inside
+ *                                 diee_mcts_batch / diee_self_play run the whole ResNet as one launch of k_ttt_net (bf16 MFMA, fp32 accumulation) on
+ *                                 the `device` given to diee_create, for every n >= 1, synchronously; the search itself stays on the host.  The first
+ *                                 HIP call of such a ctx is made here.  Without a usable GPU: DIEE_ERR_HIP, diee_last_error says so, and the ctx stays
+ *                                 on "host" and working.  Results are those of a bf16 network (within 7.3e-4 policy, 4.9e-3 value of fp32), the same
+ *                                 bits for a board whatever its row, batch or call.  Default "host": one evaluation per call (BASELINE configs[0]) is
+ *                                 where a launch and a synchronise per iteration gain least (README: measured call times).
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
  *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
  *                                 diee_self_play_refill of this ctx allocated: min(width, games of the call), whatever the call's length
