@@ -40,7 +40,7 @@ BG_STATE = np.dtype([("pts", "i1", 24), ("bar", "u1", 2), ("off", "u1", 2), ("ro
                      ("player", "i1"), ("second", "u1")])
 assert BG_STATE.itemsize == 32
 # tic-tac-toe (BASELINE configs[0]): diee_ttt_state; an Engine(game_id=GAME_TTT) runs on the host (csrc/ttt_host.cpp), its network on the
-# GPU after set_option("nn", "device") (csrc/ttt_kernels.hip)
+# GPU after set_option("nn", "device") (csrc/ttt_kernels.hip), its search too after set_option("search", "device") (csrc/ttt_search_kernels.hip)
 TTT_ACTIONS, TTT_PLANES = 9, 27
 TTT_STATE = np.dtype([("board", "i1", 9), ("player", "i1"), ("pad", "u1", 22)])
 assert TTT_STATE.itemsize == 32

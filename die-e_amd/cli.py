@@ -80,7 +80,10 @@ def main_tictactoe(args):
 
     def engine():
         e = Engine(0, GAME_TTT)
-        if os.environ.get("DIEE_TTT_NN") == "device":                                         # opt-in: the network on the GPU (k_ttt_net), the search on the host
+        if os.environ.get("DIEE_TTT_SEARCH") == "device":                                     # opt-in: network and search on the GPU (k_ttt_search)
+            e.set_option("nn", "device").set_option("search", "device")
+            print("[die-e_amd] DIEE_TTT_SEARCH=device: the tic-tac-toe search and its network run on GPU 0 (one launch per iteration); the driver stays on the host")
+        elif os.environ.get("DIEE_TTT_NN") == "device":                                       # opt-in: the network on the GPU (k_ttt_net), the search on the host
             e.set_option("nn", "device")
             print("[die-e_amd] DIEE_TTT_NN=device: the tic-tac-toe network is evaluated on GPU 0 (bf16 MFMA); the search stays on the host")
         return e

@@ -44,6 +44,11 @@ public:
     void upload(const Conv& init, const Conv* c1, const Conv* c2, const Conv& pconv, const Conv& vconv, const std::vector<float>& pfc_w,
                 const std::vector<float>& pfc_b, const std::vector<float>& vfc_w, const std::vector<float>& vfc_b);
     void forward(const diee_ttt_state* s, uint32_t n, float* policy, float* value);     // synchronous
+    // what the device search (ttt_search_device.h) shares with the network: the ctx's one stream and the packed weights
+    int device() const { return device_; }
+    hipStream_t stream() const { return stream_; }
+    const NetParams& params() const { return params_; }
+    bool ready() const { return weights_ != nullptr; }
 
 private:
     void reserve(uint32_t n);

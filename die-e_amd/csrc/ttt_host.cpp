@@ -16,6 +16,7 @@
 #include "engine.h"
 #include "search_host.h"
 #include "ttt_device.h"
+#include "ttt_search_device.h"
 
 namespace diee {
 namespace ttt {
@@ -99,9 +100,26 @@ void random_weights(uint64_t seed, float* blob) {
 Engine::Engine(int device) : device_(device) {}
 Engine::~Engine() = default;
 
+namespace {
+[[noreturn]] void unsupported_option(const std::string& key) {
+    throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has two options, `nn` and `search`; `" + key + "` belongs to a backgammon ctx");
+}
+}  // namespace
+
 void Engine::set_option(const std::string& key, const std::string& value) {
-    if (key != "nn") throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has one option, `nn`; `" + key + "` belongs to a backgammon ctx");
-    if (value == "host") { dev_.reset(); return; }
+    if (key == "search") {
+        if (value == "host") { dsearch_.reset(); return; }
+        if (value != "device") throw EngineError(DIEE_ERR_ARG, "option search: `" + value + "` is neither `host` nor `device`");
+        if (!dev_) throw EngineError(DIEE_ERR_ARG, "option search = device needs option nn = device: the device search evaluates the device network");
+        if (!dsearch_) dsearch_.reset(new DeviceSearch(*dev_));              // buffers come with the first search
+        return;
+    }
+    if (key != "nn") unsupported_option(key);
+    if (value == "host") {
+        if (dsearch_) throw EngineError(DIEE_ERR_ARG, "option nn = host while option search is `device`: set search = host first");
+        dev_.reset();
+        return;
+    }
     if (value != "device") throw EngineError(DIEE_ERR_ARG, "option nn: `" + value + "` is neither `host` nor `device`");
     if (dev_) return;
     std::unique_ptr<DeviceNet> d(new DeviceNet(device_));                // throws DIEE_ERR_HIP without a usable GPU: dev_ stays empty
@@ -109,7 +127,8 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     try { if (loaded()) upload(); } catch (...) { dev_.reset(); throw; }
 }
 std::string Engine::get_option(const std::string& key) const {
-    if (key != "nn") throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has one option, `nn`; `" + key + "` belongs to a backgammon ctx");
+    if (key == "search") return dsearch_ ? "device" : "host";
+    if (key != "nn") unsupported_option(key);
     return dev_ ? "device" : "host";
 }
 void Engine::upload() const { dev_->upload(init_, c1_, c2_, pconv_, vconv_, pfc_w_, pfc_b_, vfc_w_, vfc_b_); }
@@ -133,8 +152,8 @@ void Engine::load_weights(const float* blob, size_t n) {
     vfc_w_.assign(blob + L.vfw, blob + L.vfw + (size_t)VH * HW); vfc_b_.assign(blob + L.vfb, blob + L.vfb + 1);
     w_.assign(blob, blob + n);
     // a failed upload must not leave "device" answering with the previous network: the ctx falls back to "host" (which holds the new
-    // weights) and the caller gets the HIP error, as in set_option
-    if (dev_) { try { upload(); } catch (...) { dev_.reset(); throw; } }
+    // weights, and the host search with it) and the caller gets the HIP error, as in set_option
+    if (dev_) { try { upload(); } catch (...) { dsearch_.reset(); dev_.reset(); throw; } }
 }
 
 // ---- the network, fp32 ------------------------------------------------------------------------------------------------
@@ -257,8 +276,8 @@ void expand(Store& T, int idx, const float* policy_row, diee_stats* st) {
     if (st) { st->expansions += 1; st->children += (uint64_t)k; if ((uint64_t)k > st->max_children) st->max_children = (uint64_t)k; }
 }
 
-void search(const Engine& net, Store& T, const diee_ttt_state* roots, int n, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step,
-            bool quirks, diee_stats* st) {
+void host_search(const Engine& net, Store& T, const diee_ttt_state* roots, int n, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step,
+                 bool quirks, diee_stats* st) {
     std::vector<float> policy((size_t)n * A), value(n), noise(A);
     std::vector<diee_ttt_state> batch(roots, roots + n);
     net.forward(batch.data(), (uint32_t)n, policy.data(), value.data());                   // forward_policy, :104
@@ -322,18 +341,29 @@ int weighted_select(const float* w, double u01) {                      // alphaz
 }
 }  // namespace
 
+void Engine::search(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step, bool quirks, diee_stats* st,
+                    RootResult& R) const {
+    if (dsearch_) { dsearch_->run(roots, n, cfg, seed, step, quirks, st, R); return; }
+    Store T;                                                                               // alpha_parallel.rs:137: a fresh NodeStore every search
+    host_search(*this, T, roots, (int)n, cfg, seed, step, quirks, st);
+    R.probs.resize((size_t)n * A); R.n_children.resize(n); R.root_visits.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        root_probs(T, (int)i, &R.probs[(size_t)i * A]);
+        R.n_children[i] = (uint32_t)T.n_children[i];
+        R.root_visits[i] = T.visits[i];
+    }
+}
+
 void Engine::mcts_batch(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step,
                         const uint32_t*, const uint32_t*, uint32_t flags, float* visit_probs, uint32_t* n_children, float* root_visits,
                         diee_stats* stats) const {
     if (stats) memset(stats, 0, sizeof *stats);
     const auto t0 = std::chrono::steady_clock::now();
-    Store T;
-    search(*this, T, roots, (int)n, cfg, seed, step, (flags & DIEE_FLAG_REF_QUIRKS) != 0, stats);
-    for (uint32_t i = 0; i < n; ++i) {
-        root_probs(T, (int)i, visit_probs + (size_t)i * A);
-        if (n_children) n_children[i] = (uint32_t)T.n_children[i];
-        if (root_visits) root_visits[i] = T.visits[i];
-    }
+    RootResult R;
+    search(roots, n, cfg, seed, step, (flags & DIEE_FLAG_REF_QUIRKS) != 0, stats, R);
+    memcpy(visit_probs, R.probs.data(), R.probs.size() * sizeof(float));
+    if (n_children) memcpy(n_children, R.n_children.data(), (size_t)n * sizeof(uint32_t));
+    if (root_visits) memcpy(root_visits, R.root_visits.data(), (size_t)n * sizeof(float));
     if (stats) { stats->nn_rows = stats->nn_evals; stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 }
 
@@ -362,22 +392,22 @@ void Engine::self_play(uint32_t n_games, uint32_t first_game_id, const diee_mcts
     uint32_t n_live = n_games, steps = 0;
     std::vector<diee_ttt_state> roots; std::vector<uint32_t> ids;
     std::vector<float> row(A);
+    RootResult R;
     while (n_live > 0 && (max_steps == 0 || steps < max_steps)) {                          // alpha_parallel.rs:129
         roots.clear(); ids.clear();
         for (uint32_t g = 0; g < n_games; ++g) if (live[g]) { roots.push_back(states[g]); ids.push_back(g); }
-        Store T;                                                                           // :137 a fresh NodeStore every move-step
-        search(*this, T, roots.data(), (int)roots.size(), cfg, seed, steps, quirks, stats);   // :146
+        search(roots.data(), (uint32_t)roots.size(), cfg, seed, steps, quirks, stats, R);   // :137 a fresh NodeStore every move-step, :146
         for (size_t pi = 0; pi < ids.size(); ++pi) {                                       // :168-224
             const uint32_t g = ids[pi];
             bool removed = false, flushed = false;
             if (rounds[g] >= cfg.round_limit) { flush(g, 0, true); removed = true; flushed = true; }      // :172-180, no `continue`
-            if (T.n_children[pi] == 0) {                                                   // :183-189
+            if (R.n_children[pi] == 0) {                                                   // :183-189
                 rounds[g] += 1; skip_turn(states[g]);
                 if (stats) stats->plies += 1;
                 if (removed) { live[g] = 0; --n_live; if (stats) stats->games += 1; }
                 continue;
             }
-            root_probs(T, (int)pi, row.data());                                            // :164
+            memcpy(row.data(), &R.probs[pi * A], A * sizeof(float));                       // :164
             for (int a = 0; a < A; ++a) row[a] = det_powf(row[a], inv_t);                  // :165, not renormalised (Q17)
             const int a = weighted_select(row.data(), draw_uniform(seed, first_game_id + g, rounds[g], kTagSample, 0u));   // :192
             Frag f; f.player = states[g].player;                                           // :195-199

@@ -9,7 +9,8 @@
 // the batched search (src/mcts/alpha_mcts.rs:91-202) and the self-play driver (src/alphazero/alpha_parallel.rs:101-231).
 // It is reached only through diee_create(.., DIEE_GAME_TTT, ..); the backgammon path has no host fallback.
 // At the reference's batch sizes (1024 games per search) the network IS work for the chip: option "nn" = "device" (opt-in) sends
-// forward() to one launch of k_ttt_net (ttt_device.h); rules, search and driver stay here.
+// forward() to one launch of k_ttt_net (ttt_device.h); rules, search and driver stay here.  Over that, option "search" = "device" (opt-in
+// too) runs the batched search as one launch of k_ttt_search per iteration (ttt_search_device.h); the driver stays here.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -37,13 +38,24 @@ void random_weights(uint64_t seed, float* blob);
 
 struct Conv { std::vector<float> w, b; int cout = 0, cin = 0; };          // OIHW, BatchNorm folded (eval mode, eps 1e-5)
 class DeviceNet;                                                          // ttt_device.h
+class DeviceSearch;                                                       // ttt_search_device.h
+
+// what a search leaves for its callers: get_prob_tensor_parallel's rows (utils.rs:42-58) and the roots' counts
+struct RootResult {
+    std::vector<float> probs;                                             // [n][9]; a childless root: NaN
+    std::vector<uint32_t> n_children;                                     // [n]
+    std::vector<float> root_visits;                                       // [n]
+};
 
 class Engine {
 public:
     explicit Engine(int device = 0);                                      // `device`: the GPU option "nn" = "device" would use; not touched before
     ~Engine();
     // option "nn" (include/diee.h): "host" (default) = the fp32 loops below, "device" = k_ttt_net (ttt_device.h) behind forward().
-    // Every other key: DIEE_ERR_UNSUPPORTED.  A failed switch to "device" (no usable GPU: DIEE_ERR_HIP) leaves the ctx on the host path.
+    // A failed switch to "device" (no usable GPU: DIEE_ERR_HIP) leaves the ctx on the host path.
+    // option "search": "host" (default) = the batched search below on the host, "device" = k_ttt_search (ttt_search_device.h) behind mcts_batch
+    // and every move-step of self_play.  "device" needs "nn" = "device" (else DIEE_ERR_ARG), and "nn" cannot go back to "host" before "search" has.
+    // Every other key: DIEE_ERR_UNSUPPORTED.
     void set_option(const std::string& key, const std::string& value);
     std::string get_option(const std::string& key) const;
     void load_weights(const float* blob, size_t n);
@@ -60,8 +72,12 @@ public:
 
 private:
     void upload() const;                                                    // the folded weights -> dev_
+    // alpha_mcts_parallel (alpha_mcts.rs:91-202) on the path option "search" names; statistics are added to *st
+    void search(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step, bool quirks, diee_stats* st,
+                RootResult& R) const;
     int device_;
     std::unique_ptr<DeviceNet> dev_;                                        // non-null = "nn" is "device"
+    std::unique_ptr<DeviceSearch> dsearch_;                                 // non-null = "search" is "device" (dev_ is non-null then; declared after it: destroyed first)
     Conv init_, c1_[BLOCKS], c2_[BLOCKS], pconv_, vconv_;
     std::vector<float> pfc_w_, pfc_b_, vfc_w_, vfc_b_;
     std::vector<float> w_;                                                  // the blob as loaded (non-empty = loaded)

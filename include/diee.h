@@ -66,7 +66,7 @@ typedef struct {
  * self-play driver in C++ on the HOST (die-e_amd/csrc/ttt_host.cpp) and needs no GPU; its states are diee_ttt_state
  * records (cast the pointer where a prototype says diee_bg_state), policies / ps rows have 9 entries, planes 27.
  * Served for such a ctx: diee_load_weights, diee_nn_forward, diee_mcts_batch, diee_self_play (+ lifetime / error calls) and the
- * one option "nn" (below); everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no host path. */
+ * two options "nn" and "search" (below); everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no host path. */
 typedef struct {
     int8_t  board[9];          /* 0 | 1 | 2 / 3 | 4 | 5 / 6 | 7 | 8; -1 / 0 / +1            */
     int8_t  player;            /* -1 moves first, mod.rs:28-30                              */
@@ -202,7 +202,7 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *                                 a chunk is cut short where arena_log_mb would not hold a whole one).  The log does not depend on it
  *   arena_log_mb          MiB of HBM the turn log of one diee_arena_ex call may take (default 1024): a round that needs another row
  *                                 beyond it is not played, the call returns DIEE_ERR_CAPACITY
- *   nn                    "host" | "device"   TIC-TAC-TOE ctx only, and its only option (a backgammon ctx: DIEE_ERR_ARG, unknown option; any other
+ *   nn                    "host" | "device"   TIC-TAC-TOE ctx only, one of its two options (a backgammon ctx: DIEE_ERR_ARG, unknown option; any other
  *                                 key on a tic-tac-toe ctx: DIEE_ERR_UNSUPPORTED).  "device": diee_nn_forward and the network evaluations inside
  *                                 diee_mcts_batch / diee_self_play run the whole ResNet as one launch of k_ttt_net (bf16 MFMA, fp32 accumulation) on
  *                                 the `device` given to diee_create, for every n >= 1, synchronously; the search itself stays on the host.  The first
@@ -210,6 +210,13 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *                                 on "host" and working.  Results are those of a bf16 network (within 7.3e-4 policy, 4.9e-3 value of fp32), the same
  *                                 bits for a board whatever its row, batch or call.  Default "host": one evaluation per call (BASELINE configs[0]) is
  *                                 where a launch and a synchronise per iteration gain least (README: measured call times).
+ *   search                "host" | "device"   TIC-TAC-TOE ctx only, its other option.  "device": the search of diee_mcts_batch and of every move-step of
+ *                                 diee_self_play runs on the device as iterations + 1 launches of k_ttt_search (selection, expansion, backpropagation
+ *                                 and the network in one launch per iteration), one synchronise per call; the self-play driver stays on the host.
+ *                                 Same results, bit for bit, as "host" over "nn" = "device", with or without DIEE_FLAG_REF_QUIRKS.  Accepted only
+ *                                 while "nn" is "device" (else DIEE_ERR_ARG), and "nn" = "host" is DIEE_ERR_ARG until "search" is "host" again; any
+ *                                 other value: DIEE_ERR_ARG.  Roots must hold cells of -1 / 0 / +1 and a player of -1 / +1 (else DIEE_ERR_ARG); a
+ *                                 buffer that cannot be allocated is DIEE_ERR_HIP and no partial result.  Default "host".
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
  *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
  *                                 diee_self_play_refill of this ctx allocated: min(width, games of the call), whatever the call's length
