@@ -49,7 +49,7 @@ assert TTT_STATE.itemsize == 32
 # of include/diee_dev.h are listed in DEV_EXPORTS
 EXPORTS = [
     "diee_create", "diee_destroy", "diee_last_error", "diee_version", "diee_set_option", "diee_get_option", "diee_device_pci_bus_id", "diee_weights_count",
-    "diee_random_weights", "diee_load_weights", "diee_nn_forward", "diee_mcts_batch", "diee_mcts_vanilla_batch", "diee_self_play",
+    "diee_random_weights", "diee_load_weights", "diee_nn_forward", "diee_mcts_batch", "diee_mcts_vanilla_batch", "diee_ttt_mcts_vanilla_batch", "diee_self_play",
     "diee_self_play_multi", "diee_self_play_refill", "diee_arena", "diee_arena_ex", "diee_free_arena_log", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
     "diee_train_conv3x3", "diee_train_im2col3x3",
     "diee_train_scratch_floats", "diee_train_bn_relu_fwd", "diee_train_bn_relu_bwd", "diee_train_colsum",
@@ -191,6 +191,8 @@ def load_library(path=None):
     L.diee_mcts_batch.restype = C.c_int
     L.diee_mcts_vanilla_batch.argtypes = [vp, vp, u32, vp, u64, vp, vp, u32, vp, vp, vp, vp, u32, vp]
     L.diee_mcts_vanilla_batch.restype = C.c_int
+    L.diee_ttt_mcts_vanilla_batch.argtypes = [vp, vp, u32, vp, u64, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.diee_ttt_mcts_vanilla_batch.restype = C.c_int
     L.diee_self_play.argtypes = [vp, u32, u32, vp, f32, u64, u32, u32, vp, vp]; L.diee_self_play.restype = C.c_int
     L.diee_self_play_multi.argtypes = [vp, vp, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_multi.restype = C.c_int
     L.diee_self_play_refill.argtypes = [vp, vp, u32, u32, vp, f32, u32, u32, vp, vp]; L.diee_self_play_refill.restype = C.c_int
@@ -470,6 +472,23 @@ class Engine:
                                                   FLAG_REF_QUIRKS if ref_quirks else 0, plays.ctypes.data, nch.ctypes.data,
                                                   cv.ctypes.data, cw.ctypes.data, cap, C.byref(st)))
         return {"plays": plays, "n_children": nch, "child_visits": cv, "child_values": cw, "stats": st.as_dict()}
+
+    def ttt_mct_search(self, states, cfg, seed=0, game_ids=None, rounds=None, ref_quirks=True):
+        """mct_search per root on a tic-tac-toe engine (diee_ttt_mcts_vanilla_batch; no weights needed; on the host, or k_ttt_vanilla while
+        option "search" is "device") -> dict(moves uint8 [n] (10 = EMPTY_MOVE), n_children, child_visits / child_values [n,9] in
+        creation order, stats)"""
+        s = _states(states); n = len(s)
+        moves = np.full(n, 10, dtype=np.uint8)
+        nch = np.zeros(n, dtype=np.uint32)
+        cv = np.zeros((n, TTT_ACTIONS), dtype=np.float32); cw = np.zeros((n, TTT_ACTIONS), dtype=np.float32)
+        gi = None if game_ids is None else np.ascontiguousarray(game_ids, dtype=np.uint32)
+        rd = None if rounds is None else np.ascontiguousarray(rounds, dtype=np.uint32)
+        st = VanillaStats()
+        self._chk(self._L.diee_ttt_mcts_vanilla_batch(self._h, s.ctypes.data, n, C.byref(cfg), seed,
+                                                      None if gi is None else gi.ctypes.data, None if rd is None else rd.ctypes.data,
+                                                      FLAG_REF_QUIRKS if ref_quirks else 0, moves.ctypes.data, nch.ctypes.data,
+                                                      cv.ctypes.data, cw.ctypes.data, C.byref(st)))
+        return {"moves": moves, "n_children": nch, "child_visits": cv, "child_values": cw, "stats": st.as_dict()}
 
     def _take_fragments(self, fr, out, copy=True):
         """diee_fragments -> numpy.  copy=True: arrays of their own, the engine's blocks go back at once.  copy=False: views of

@@ -82,7 +82,7 @@ def main_tictactoe(args):
         e = Engine(0, GAME_TTT)
         if os.environ.get("DIEE_TTT_SEARCH") == "device":                                     # opt-in: network and search on the GPU (k_ttt_search)
             e.set_option("nn", "device").set_option("search", "device")
-            print("[die-e_amd] DIEE_TTT_SEARCH=device: the tic-tac-toe search and its network run on GPU 0 (one launch per iteration); the driver stays on the host")
+            print("[die-e_amd] DIEE_TTT_SEARCH=device: the tic-tac-toe searches and the network run on GPU 0 (k_ttt_search, k_ttt_vanilla); the driver stays on the host")
         elif os.environ.get("DIEE_TTT_NN") == "device":                                       # opt-in: the network on the GPU (k_ttt_net), the search on the host
             e.set_option("nn", "device")
             print("[die-e_amd] DIEE_TTT_NN=device: the tic-tac-toe network is evaluated on GPU 0 (bf16 MFMA); the search stays on the host")
@@ -110,8 +110,12 @@ def main_tictactoe(args):
                 return None
             e = engine(); e.load_weights(load_model(path)); return e
         a1, a2 = Agent.parse(args.agent_one), Agent.parse(args.agent_two)
-        print(play_tictactoe(Player(a1, model(args.model_path_one)), Player(a2, model(args.model_path_two)), mcts_config_from(conf),
-                             float(conf["temperature"])))
+        m1, m2 = model(args.model_path_one), model(args.model_path_two)
+        if a1 == Agent.MCTS and m1 is None:                                                   # Agent::Mcts needs no weights: a weightless engine searches
+            m1 = engine()
+        if a2 == Agent.MCTS and m2 is None:
+            m2 = engine()
+        print(play_tictactoe(Player(a1, m1), Player(a2, m2), mcts_config_from(conf), float(conf["temperature"])))
     return 0
 
 

@@ -241,6 +241,16 @@ diee_status diee_mcts_vanilla_batch(diee_ctx* c, const diee_bg_state* roots, uin
     API_END(c)
 }
 
+diee_status diee_ttt_mcts_vanilla_batch(diee_ctx* c, const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg* cfg, uint64_t seed,
+                                        const uint32_t* game_ids, const uint32_t* rounds, uint32_t flags, uint8_t* moves, uint32_t* n_children,
+                                        float* child_visits, float* child_values, diee_vanilla_stats* stats) {
+    API_BEGIN(c)
+    if (!c->ttt) throw EngineError(DIEE_ERR_UNSUPPORTED, "this entry point needs a tic-tac-toe ctx (a backgammon ctx: diee_mcts_vanilla_batch)");
+    if (!roots || !cfg || !moves) throw EngineError(DIEE_ERR_ARG, "null pointer");
+    c->ttt->mcts_vanilla_batch(roots, n, *cfg, seed, game_ids, rounds, flags, moves, n_children, child_visits, child_values, stats);
+    API_END(c)
+}
+
 diee_status diee_self_play(diee_ctx* c, uint32_t n_games, uint32_t first_game_id, const diee_mcts_cfg* cfg,
                            float temperature, uint64_t seed, uint32_t flags, uint32_t max_steps,
                            diee_fragments* out, diee_stats* stats) {

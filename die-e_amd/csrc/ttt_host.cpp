@@ -17,6 +17,8 @@
 #include "search_host.h"
 #include "ttt_device.h"
 #include "ttt_search_device.h"
+#include "ttt_vanilla_device.h"
+#include "vanilla_host.h"
 
 namespace diee {
 namespace ttt {
@@ -108,9 +110,10 @@ namespace {
 
 void Engine::set_option(const std::string& key, const std::string& value) {
     if (key == "search") {
-        if (value == "host") { dsearch_.reset(); return; }
+        if (value == "host") { dsearch_.reset(); dvanilla_.reset(); return; }
         if (value != "device") throw EngineError(DIEE_ERR_ARG, "option search: `" + value + "` is neither `host` nor `device`");
         if (!dev_) throw EngineError(DIEE_ERR_ARG, "option search = device needs option nn = device: the device search evaluates the device network");
+        if (!dvanilla_) dvanilla_.reset(new DeviceVanilla(*dev_));
         if (!dsearch_) dsearch_.reset(new DeviceSearch(*dev_));              // buffers come with the first search
         return;
     }
@@ -153,7 +156,7 @@ void Engine::load_weights(const float* blob, size_t n) {
     w_.assign(blob, blob + n);
     // a failed upload must not leave "device" answering with the previous network: the ctx falls back to "host" (which holds the new
     // weights, and the host search with it) and the caller gets the HIP error, as in set_option
-    if (dev_) { try { upload(); } catch (...) { dsearch_.reset(); dev_.reset(); throw; } }
+    if (dev_) { try { upload(); } catch (...) { dsearch_.reset(); dvanilla_.reset(); dev_.reset(); throw; } }
 }
 
 // ---- the network, fp32 ------------------------------------------------------------------------------------------------
@@ -442,6 +445,133 @@ void Engine::self_play(uint32_t n_games, uint32_t first_game_id, const diee_mcts
     memcpy(out->outcome, o_outcome.data(), nf); memcpy(out->ps, o_ps.data(), nf * A * sizeof(float));
     memcpy(out->state, o_state.data(), nf * PLANES * sizeof(float)); memcpy(out->game, o_game.data(), nf * sizeof(uint32_t));
     out->n = (uint32_t)nf;
+}
+
+// ---- Agent::Mcts: mct_search (simple_mcts.rs:10-39) with Node::expand / simulate (node.rs:118-137,176-196), one root at a time ------------
+namespace {
+struct VNode {                       // node.rs:10-22; expandable_moves is the first n_moves - n_children of the node's empty cells
+    diee_ttt_state state;
+    int parent, n_children, child[9];
+    uint32_t visits;
+    float value;
+};
+inline float result_for(int winner, int player) { return winner == player ? 1.0f : (winner == -player ? -1.0f : 0.0f); }
+
+struct VanillaRoot { uint8_t move; uint32_t n_children; float child_visits[9], child_values[9]; };
+
+VanillaRoot vanilla_search_host(const diee_ttt_state& root, const diee_mcts_cfg& cfg, const std::vector<float>& ln, uint64_t seed, uint32_t game,
+                                uint32_t round, bool quirks, diee_vanilla_stats* st) {
+    VanillaRoot R{};
+    R.move = 10;                                                                           // TicTacToe::EMPTY_MOVE, mod.rs:18
+    int winner = 0;
+    if (check_winner(root, winner)) return R;                                              // simple_mcts.rs:12-14
+    const int player = root.player;
+    std::vector<VNode> T;
+    T.reserve((size_t)cfg.iterations + 1);
+    auto add = [&](const diee_ttt_state& s, int parent) { VNode nd{}; nd.state = s; nd.parent = parent; T.push_back(nd); return (int)T.size() - 1; };
+    add(root, -1);
+    uint8_t mv[9];
+    for (uint32_t it = 0; it < cfg.iterations; ++it) {                                     // :17-37
+        int idx = 0;
+        uint64_t depth = 0;
+        while (T[idx].n_children != 0 && T[idx].n_children == valid_moves(T[idx].state, mv)) {     // :88-94
+            const VNode& nd = T[idx];
+            const float cl = cfg.c * ln[nd.visits];
+            int best = -1;
+            float ub = 0.f;
+            for (int j = 0; j < nd.n_children; ++j) {                                      // node.rs:86-96, max_by: the last of equal maxima
+                const VNode& ch = T[nd.child[j]];
+                const float v = (float)ch.visits;
+                const float q = ch.value / v;
+                const float e = std::sqrt(cl / v);
+                const float un = q + e;
+                if (best < 0 || !(ub > un)) { best = nd.child[j]; ub = un; }
+            }
+            idx = best; ++depth;
+        }
+        st->iterations += 1; st->depth_sum += depth;
+        float res = 0.f;
+        int from = idx;
+        if (check_winner(T[idx].state, winner)) {                                          // :25-30
+            res = result_for(winner, player);
+            st->terminal_hits += 1;
+        } else {
+            const int k = valid_moves(T[idx].state, mv);                                   // expand: expandable_moves.pop()
+            diee_ttt_state sim = T[idx].state;
+            apply_move(sim, mv[k - 1 - T[idx].n_children]);
+            from = add(sim, idx);
+            T[idx].child[T[idx].n_children++] = from;
+            st->expansions += 1; st->rollouts += 1;
+            if (quirks) {                                                                  // Q22: the loop looks at the node's own state and plays nothing
+                if (cfg.round_limit > 0 && check_winner(sim, winner)) { res = result_for(winner, player); st->rollout_decided += 1; }
+            } else {
+                for (uint32_t p = 0; p < cfg.round_limit; ++p) {
+                    if (check_winner(sim, winner)) { res = result_for(winner, player); st->rollout_decided += 1; break; }
+                    const int k1 = valid_moves(sim, mv);
+                    int pick = (int)(draw_uniform(seed, game, round, kTagVanilla, (it << 12) | (1u + p)) * (double)k1);
+                    pick = pick > k1 - 1 ? k1 - 1 : pick;
+                    apply_move(sim, mv[pick]);
+                    st->rollout_plies += 1;
+                }
+            }
+        }
+        for (int i = from; i >= 0; i = T[i].parent) { T[i].visits += 1u; T[i].value += res; }      // :96-103: the same sign at every level
+    }
+    const VNode& r = T[0];
+    R.n_children = (uint32_t)r.n_children;
+    uint32_t bv = 0;
+    for (int j = 0; j < r.n_children; ++j) {                                               // :71-86 max_by_key(visits): the last of equal maxima
+        const VNode& ch = T[r.child[j]];
+        R.child_visits[j] = (float)ch.visits; R.child_values[j] = ch.value;
+        if (ch.visits >= bv) {
+            bv = ch.visits;
+            for (int cidx = 0; cidx < 9; ++cidx) if (r.state.board[cidx] == 0 && ch.state.board[cidx] != 0) R.move = (uint8_t)cidx;
+        }
+    }
+    return R;
+}
+}  // namespace
+
+void Engine::mcts_vanilla_batch(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, const uint32_t* game_ids,
+                                const uint32_t* rounds, uint32_t flags, uint8_t* moves, uint32_t* n_children, float* child_visits,
+                                float* child_values, diee_vanilla_stats* stats) const {
+    diee_vanilla_stats st{};
+    if (stats) *stats = st;
+    vanilla_check_cfg(cfg);
+    // a node keeps its board at 2 bits per cell and its player in one: what the rules produce from any legal position.  Then a node that
+    // is not a finished game always has a move
+    for (uint32_t i = 0; i < n; ++i) {
+        bool ok = roots[i].player == 1 || roots[i].player == -1;
+        for (int cidx = 0; cidx < 9; ++cidx) ok = ok && roots[i].board[cidx] >= -1 && roots[i].board[cidx] <= 1;
+        if (!ok) throw EngineError(DIEE_ERR_ARG, "Agent::Mcts: root " + std::to_string(i) + " has a cell or a player outside -1 / 0 / +1");
+    }
+    if (!n) return;
+    const bool quirks = (flags & DIEE_FLAG_REF_QUIRKS) != 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto answer = [&](uint32_t i, uint32_t move, uint32_t nc, const float* cv, const float* cw) {
+        moves[i] = (uint8_t)move;
+        if (n_children) n_children[i] = nc;
+        if (child_visits) memcpy(child_visits + (size_t)i * A, cv, A * sizeof(float));
+        if (child_values) memcpy(child_values + (size_t)i * A, cw, A * sizeof(float));
+    };
+    if (dvanilla_) {
+        const VanillaOut* out = dvanilla_->run(roots, n, cfg, seed, game_ids, rounds, quirks);     // throws before anything is written
+        for (uint32_t i = 0; i < n; ++i) {
+            const VanillaOut& o = out[i];
+            answer(i, o.move, o.n_children, o.child_visits, o.child_values);
+            st.iterations += o.cnt[kVcIterations]; st.expansions += o.cnt[kVcExpansions]; st.terminal_hits += o.cnt[kVcTerminal];
+            st.rollouts += o.cnt[kVcRollouts]; st.rollout_plies += o.cnt[kVcPlies]; st.rollout_decided += o.cnt[kVcDecided];
+            st.depth_sum += o.cnt[kVcDepthSum];
+        }
+    } else {
+        std::vector<float> ln((size_t)cfg.iterations + 2, 0.0f);                                   // the table the device search reads
+        for (size_t k = 1; k < ln.size(); ++k) ln[k] = (float)std::log((double)k);
+        for (uint32_t i = 0; i < n; ++i) {
+            const VanillaRoot r = vanilla_search_host(roots[i], cfg, ln, seed, game_ids ? game_ids[i] : i, rounds ? rounds[i] : 0u, quirks, &st);
+            answer(i, r.move, r.n_children, r.child_visits, r.child_values);
+        }
+    }
+    if (stats) { *stats = st; stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 }
 
 }  // namespace ttt

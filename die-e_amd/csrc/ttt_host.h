@@ -11,6 +11,7 @@
 // At the reference's batch sizes (1024 games per search) the network IS work for the chip: option "nn" = "device" (opt-in) sends
 // forward() to one launch of k_ttt_net (ttt_device.h); rules, search and driver stay here.  Over that, option "search" = "device" (opt-in
 // too) runs the batched search as one launch of k_ttt_search per iteration (ttt_search_device.h); the driver stays here.
+// Agent::Mcts (mcts_vanilla_batch, no network) follows option "search" too: here by default, k_ttt_vanilla (ttt_vanilla_device.h) on "device".
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -39,6 +40,7 @@ void random_weights(uint64_t seed, float* blob);
 struct Conv { std::vector<float> w, b; int cout = 0, cin = 0; };          // OIHW, BatchNorm folded (eval mode, eps 1e-5)
 class DeviceNet;                                                          // ttt_device.h
 class DeviceSearch;                                                       // ttt_search_device.h
+class DeviceVanilla;                                                      // ttt_vanilla_device.h
 
 // what a search leaves for its callers: get_prob_tensor_parallel's rows (utils.rs:42-58) and the roots' counts
 struct RootResult {
@@ -53,8 +55,8 @@ public:
     ~Engine();
     // option "nn" (include/diee.h): "host" (default) = the fp32 loops below, "device" = k_ttt_net (ttt_device.h) behind forward().
     // A failed switch to "device" (no usable GPU: DIEE_ERR_HIP) leaves the ctx on the host path.
-    // option "search": "host" (default) = the batched search below on the host, "device" = k_ttt_search (ttt_search_device.h) behind mcts_batch
-    // and every move-step of self_play.  "device" needs "nn" = "device" (else DIEE_ERR_ARG), and "nn" cannot go back to "host" before "search" has.
+    // option "search": "host" (default) = both searches below on the host, "device" = k_ttt_search (ttt_search_device.h) behind mcts_batch
+    // and every move-step of self_play, and k_ttt_vanilla (ttt_vanilla_device.h) behind mcts_vanilla_batch.  "device" needs "nn" = "device" (else DIEE_ERR_ARG), and "nn" cannot go back to "host" before "search" has.
     // Every other key: DIEE_ERR_UNSUPPORTED.
     void set_option(const std::string& key, const std::string& value);
     std::string get_option(const std::string& key) const;
@@ -69,6 +71,10 @@ public:
                     float* root_visits, diee_stats* stats) const;
     void self_play(uint32_t n_games, uint32_t first_game_id, const diee_mcts_cfg& cfg, float temperature, uint64_t seed,
                    uint32_t flags, uint32_t max_steps, diee_fragments* out, diee_stats* stats) const;
+    // mct_search (simple_mcts.rs:10-39) per root, Agent::Mcts: diee_ttt_mcts_vanilla_batch of include/diee.h.  Needs no weights.
+    void mcts_vanilla_batch(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, const uint32_t* game_ids,
+                            const uint32_t* rounds, uint32_t flags, uint8_t* moves, uint32_t* n_children, float* child_visits,
+                            float* child_values, diee_vanilla_stats* stats) const;
 
 private:
     void upload() const;                                                    // the folded weights -> dev_
@@ -78,6 +84,7 @@ private:
     int device_;
     std::unique_ptr<DeviceNet> dev_;                                        // non-null = "nn" is "device"
     std::unique_ptr<DeviceSearch> dsearch_;                                 // non-null = "search" is "device" (dev_ is non-null then; declared after it: destroyed first)
+    std::unique_ptr<DeviceVanilla> dvanilla_;                               // set and cleared with dsearch_
     Conv init_, c1_[BLOCKS], c2_[BLOCKS], pconv_, vconv_;
     std::vector<float> pfc_w_, pfc_b_, vfc_w_, vfc_b_;
     std::vector<float> w_;                                                  // the blob as loaded (non-empty = loaded)

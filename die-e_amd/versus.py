@@ -494,10 +494,13 @@ def play_device(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=
 
 
 # ---- the same arena for tic-tac-toe (play::<TicTacToe>, versus.rs:160-268 is generic over LearnableGame) ------------------
-def play_tictactoe(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400):
-    """Model / Random agents on the tic-tac-toe host engine (BASELINE configs[0]); player1 plays side -1 in every game, the
-    second half of the games starts after a skip_turn() (:172-174), a draw (check_winner = Some(0)) has no winner"""
+def play_tictactoe(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, vanilla_rollouts=None):
+    """Model / Mcts / Random agents on the tic-tac-toe engine (BASELINE configs[0]); player1 plays side -1 in every game, the
+    second half of the games starts after a skip_turn() (:172-174), a draw (check_winner = Some(0)) has no winner.  An Mcts player
+    searches on its engine (Player.model, no weights needed: Engine.ttt_mct_search); vanilla_rollouts as in play()"""
     from . import TTT_ACTIONS, ttt_apply_move, ttt_check_winner, ttt_new, ttt_valid_moves
+    if vanilla_rollouts is None:
+        vanilla_rollouts = Agent.MCTS in (player1.player_type, player2.player_type) and vanilla_rollouts_from_env()
     states = ttt_new(num_games)
     states["player"][num_games // 2:] = 1
     alive = np.ones(num_games, dtype=bool)
@@ -532,9 +535,15 @@ def play_tictactoe(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_gam
                     vm = ttt_valid_moves(states[g])
                     if vm:
                         acts[int(g)] = vm[min(int(uni[k] * len(vm)), len(vm) - 1)]
+            elif pl.model is None:
+                raise NotImplementedError("Agent::Mcts (vanilla MCTS with rollouts) runs on the engine: give the player a tic-tac-toe "
+                                          "engine (Player.model); it needs no weights")
             else:
-                raise NotImplementedError("Agent::Mcts (vanilla MCTS with rollouts) runs on the backgammon engine only; the tic-tac-toe "
-                                          "Mcts agent is not provided")
+                r = pl.model.ttt_mct_search(states[ids], mcts_config, seed, ids.astype(np.uint32), np.full(len(ids), round_count, dtype=np.uint32),
+                                            ref_quirks=not vanilla_rollouts)
+                for k, g in enumerate(ids):
+                    if r["moves"][k] != 10:                                               # EMPTY_MOVE skips the turn
+                        acts[int(g)] = int(r["moves"][k])
         round_count += 1                                                                 # :219
         for g in np.concatenate(sides):
             g = int(g)

@@ -65,8 +65,9 @@ typedef struct {
  * a ctx created with DIEE_GAME_TTT runs rules, the 64-filter 4-block ResNet (mod.rs:20-24), the search and the
  * self-play driver in C++ on the HOST (die-e_amd/csrc/ttt_host.cpp) and needs no GPU; its states are diee_ttt_state
  * records (cast the pointer where a prototype says diee_bg_state), policies / ps rows have 9 entries, planes 27.
- * Served for such a ctx: diee_load_weights, diee_nn_forward, diee_mcts_batch, diee_self_play (+ lifetime / error calls) and the
- * two options "nn" and "search" (below); everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no host path. */
+ * Served for such a ctx: diee_load_weights, diee_nn_forward, diee_mcts_batch, diee_ttt_mcts_vanilla_batch, diee_self_play (+ lifetime /
+ * error calls) and the two options "nn" and "search" (below); everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no
+ * host path. */
 typedef struct {
     int8_t  board[9];          /* 0 | 1 | 2 / 3 | 4 | 5 / 6 | 7 | 8; -1 / 0 / +1            */
     int8_t  player;            /* -1 moves first, mod.rs:28-30                              */
@@ -217,6 +218,9 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *                                 while "nn" is "device" (else DIEE_ERR_ARG), and "nn" = "host" is DIEE_ERR_ARG until "search" is "host" again; any
  *                                 other value: DIEE_ERR_ARG.  Roots must hold cells of -1 / 0 / +1 and a player of -1 / +1 (else DIEE_ERR_ARG); a
  *                                 buffer that cannot be allocated is DIEE_ERR_HIP and no partial result.  Default "host".
+ *                                 The option names where BOTH searches of the ctx run: diee_ttt_mcts_vanilla_batch (Agent::Mcts, no network) runs
+ *                                 as launches of k_ttt_vanilla, up to 4096 whole iterations per game and launch, with the same bits as on "host".
+ *                                 That search needs no weights: a weightless ctx may set "nn" = "device", then "search" = "device".
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
  *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
  *                                 diee_self_play_refill of this ctx allocated: min(width, games of the call), whatever the call's length
@@ -307,6 +311,35 @@ diee_status diee_mcts_vanilla_batch(diee_ctx*, const diee_bg_state* roots, uint3
                                     uint64_t seed, const uint32_t* game_ids, const uint32_t* rounds, uint32_t flags,
                                     int8_t* plays, uint32_t* n_children, float* child_visits, float* child_values,
                                     uint32_t cap, diee_vanilla_stats* stats);
+
+/* ---- level 1, Agent::Mcts for TIC-TAC-TOE: the search above carried over to the game, for a tic-tac-toe ctx (a backgammon ctx:
+ * DIEE_ERR_UNSUPPORTED; diee_mcts_vanilla_batch in turn keeps refusing a tic-tac-toe ctx).  The ctx needs no weights.  Runs on the host
+ * (ttt_host.cpp) while option "search" is "host", the default, and as launches of k_ttt_vanilla while it is "device"; both give the same
+ * bits.  Per root, player = root.player; a root that is a finished game answers 10 and runs no iteration (simple_mcts.rs:12-14).
+ *   select    as above: fp32 value / visits + sqrt((c * ln(parent.visits)) / visits), ln from the host-built table, of equal maxima the last
+ *             created, a NaN score comparing Equal (the fold `if !(best > u) { best = child }` in creation order);
+ *   the selected node is a finished game: +1 / -1 / 0 backpropagated from it for winner == player, winner == -player, a draw (check_winner
+ *             is Some(0) on a full board, src/tictactoe/mod.rs:59-79);
+ *   otherwise one child is created: a node's moves are its empty cells in ascending order, its j-th child takes move number count - 1 - j
+ *             (expandable_moves.pop()), apply_move; simulate from the child, backpropagate from the child, the same sign at every level;
+ *   simulate  without DIEE_FLAG_REF_QUIRKS, round_limit times { the state has a winner or is full: return +1 / -1 / 0 from `player`'s view;
+ *             otherwise play moves[min(int(u * count), count - 1)] }, then 0 (a state that became final on the last ply is not looked at);
+ *             u = the uniform of Philox counter (game_id, round, TAG_VANILLA, iteration << 12 | 1 + p) for ply p.  With the flag (Q22)
+ *             nothing is played: +1 / -1 / 0 if round_limit > 0 and the node simulated from is a finished game, otherwise 0;
+ *   answer    moves[i] = the cell 0 .. 8 of the root's most visited child, the last created of equal ones; 10 (TicTacToe::EMPTY_MOVE,
+ *             mod.rs:18) if the root has no children.
+ * iterations >= 2^20 or round_limit > 4094: DIEE_ERR_ARG (the counter layout).  Roots must hold cells of -1 / 0 / +1 and a player of -1 / +1,
+ * else DIEE_ERR_ARG; then a node that is not finished always has a move and dead_end_hits stays 0.  cfg->c is not checked.  game_ids /
+ * rounds may be NULL (i / 0).  n_children [n], child_visits / child_values [n][9] in creation order, zero beyond the count (each or NULL).
+ * diee_vanilla_stats as above; rollout_plies counts plies actually played, rollout_decided the rollouts that ended on a finished game (a draw
+ * included).  On "device" a buffer that cannot be had is DIEE_ERR_HIP with no partial result. */
+diee_status diee_ttt_mcts_vanilla_batch(diee_ctx*, const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg* cfg,
+                                        uint64_t seed, const uint32_t* game_ids, const uint32_t* rounds, uint32_t flags,
+                                        uint8_t* moves        /* [n]: the cell 0..8, or 10 = TicTacToe::EMPTY_MOVE (mod.rs:18) */,
+                                        uint32_t* n_children  /* [n] or NULL */,
+                                        float* child_visits   /* [n][9] or NULL: creation order, zero beyond the count */,
+                                        float* child_values   /* [n][9] or NULL */,
+                                        diee_vanilla_stats* stats /* or NULL */);
 
 /* ---- level 2: AlphaZero::self_play_parallel, alpha_parallel.rs:101-231
  * n_games = num_self_play_batches; first_game_id offsets the RNG keys (rank * n_games when games
