@@ -11,6 +11,7 @@ reference's tests:
                                                   -> Engine.alpha_mcts_parallel
     AlphaZero::self_play_parallel (src/alphazero/alpha_parallel.rs:101) -> Engine.self_play_parallel
     play (src/versus.rs:160-268)                  -> arena / Engine.arena (die-e_amd/versus.py: play_device)
+    play::<TicTacToe>                             -> ttt_arena / Engine.ttt_arena (versus.py: play_tictactoe_device)
     mct_search (src/mcts/simple_mcts.rs:10-39)    -> Engine.mct_search (Agent::Mcts)
 
 There is no CPU fallback: the library must load and a GPU must be present, otherwise the
@@ -50,7 +51,7 @@ assert TTT_STATE.itemsize == 32
 EXPORTS = [
     "diee_create", "diee_destroy", "diee_last_error", "diee_version", "diee_set_option", "diee_get_option", "diee_device_pci_bus_id", "diee_weights_count",
     "diee_random_weights", "diee_load_weights", "diee_nn_forward", "diee_mcts_batch", "diee_mcts_vanilla_batch", "diee_ttt_mcts_vanilla_batch", "diee_self_play",
-    "diee_self_play_multi", "diee_self_play_refill", "diee_arena", "diee_arena_ex", "diee_free_arena_log", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
+    "diee_self_play_multi", "diee_self_play_refill", "diee_arena", "diee_arena_ex", "diee_free_arena_log", "diee_ttt_arena", "diee_set_invariant_nn", "diee_train_pack_conv3x3", "diee_train_pack_conv3x3_multi",
     "diee_train_conv3x3", "diee_train_im2col3x3",
     "diee_train_scratch_floats", "diee_train_bn_relu_fwd", "diee_train_bn_relu_bwd", "diee_train_colsum",
     "diee_train_set_bn_coop", "diee_train_bn_coop_timeouts",
@@ -199,6 +200,7 @@ def load_library(path=None):
     L.diee_arena.argtypes = [vp, C.c_int, vp, C.c_int, u32, vp, f32, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]; L.diee_arena.restype = C.c_int
     L.diee_arena_ex.argtypes = [vp, C.c_int, vp, C.c_int, u32, vp, f32, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]; L.diee_arena_ex.restype = C.c_int
     L.diee_free_arena_log.argtypes = [vp]; L.diee_free_arena_log.restype = None
+    L.diee_ttt_arena.argtypes = [vp, C.c_int, vp, C.c_int, u32, vp, f32, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp]; L.diee_ttt_arena.restype = C.c_int
     L.diee_set_invariant_nn.argtypes = [vp, C.c_int]; L.diee_set_invariant_nn.restype = C.c_int
     L.diee_train_pack_conv3x3.argtypes = [vp, vp, C.c_int, vp]; L.diee_train_pack_conv3x3.restype = C.c_int
     L.diee_train_pack_conv3x3_multi.argtypes = [C.POINTER(vp), C.c_int, vp, vp]; L.diee_train_pack_conv3x3_multi.restype = C.c_int
@@ -568,6 +570,10 @@ class Engine:
         return arena(self, agent1, other, agent2, n_games, cfg, temperature, seed, round_limit, max_rounds, ref_quirks, invariant_nn,
                      record_turns, flags2)
 
+    def ttt_arena(self, agent1, other, agent2, n_games, cfg, temperature=1.25, seed=0xD1EE0001, round_limit=400, max_rounds=0, flags=(FLAG_REF_QUIRKS,) * 2):
+        """ttt_arena() below with this tic-tac-toe engine as player 1"""
+        return ttt_arena(self, agent1, other, agent2, n_games, cfg, temperature, seed, round_limit, max_rounds, flags)
+
 
 def arena(engine1, agent1, engine2, agent2, n_games, cfg, temperature=1.25, seed=0xD1EE0001, round_limit=400, max_rounds=0,
           ref_quirks=True, invariant_nn=False, record_turns=False, flags2=None):
@@ -612,6 +618,28 @@ def arena(engine1, agent1, engine2, agent2, n_games, cfg, temperature=1.25, seed
     return {"wins_p1": res.wins_p1, "wins_p2": res.wins_p2, "draws": res.draws, "rounds": res.rounds,
             "illegal_decodes": res.illegal_decodes, "seconds": res.seconds, "winner": winner, "retired_round": rround,
             "retired_side": rside, "initial_states": init, "final_states": final, "stats": [sts[0].as_dict(), sts[1].as_dict()], **extra}
+
+
+def ttt_arena(engine1, agent1, engine2, agent2, n_games, cfg, temperature=1.25, seed=0xD1EE0001, round_limit=400, max_rounds=0,
+              flags=(FLAG_REF_QUIRKS,) * 2):
+    """play::<TicTacToe> in one engine call (diee_ttt_arena): tic-tac-toe engines, engine1 is player 1 and hosts the call (engine2 when
+    engine1 is None; a Random or Mcts agent may come without an engine).  The hosting engine's option "search" names the path: "host" = a
+    round loop in the engine, "device" = every round on the GPU.  flags = the flag word (FLAG_*) of each player's searches.  -> dict(wins_p1,
+    wins_p2, draws, rounds, seconds, winner int8 [n], retired_round uint32 [n] (0xFFFFFFFF: still alive, max_rounds), retired_side int8
+    [n], final_states, stats [per player])"""
+    host = engine1 if engine1 is not None else engine2
+    if host is None:
+        raise ValueError("the arena needs an engine")
+    n = int(n_games)
+    winner = np.zeros(n, dtype=np.int8); rside = np.zeros(n, dtype=np.int8); rround = np.zeros(n, dtype=np.uint32)
+    final = np.zeros(n, dtype=TTT_STATE)
+    res = ArenaResult(); sts = (Stats * 2)()
+    fl = (C.c_uint32 * 2)(int(flags[0]), int(flags[1]))
+    host._chk(host._L.diee_ttt_arena(None if engine1 is None else engine1._h, int(agent1), None if engine2 is None else engine2._h, int(agent2), n,
+                                     C.byref(cfg), temperature, seed, int(round_limit), int(max_rounds), fl, C.byref(res), winner.ctypes.data,
+                                     rround.ctypes.data, rside.ctypes.data, final.ctypes.data, C.byref(sts)))
+    return {"wins_p1": res.wins_p1, "wins_p2": res.wins_p2, "draws": res.draws, "rounds": res.rounds, "seconds": res.seconds, "winner": winner,
+            "retired_round": rround, "retired_side": rside, "final_states": final, "stats": [sts[0].as_dict(), sts[1].as_dict()]}
 
 
 # ---- LearnableGame for TicTacToe (src/tictactoe/mod.rs), host functions of the C ABI -------------------------------------

@@ -581,7 +581,11 @@ class AlphaZero:
     # ---- play_vs_best_model / play_vs_model, alpha_versus.rs:16-81 ----
     def play_vs_best_model(self, n_games=400):
         from .versus import Agent, Player, play
-        if self.game is TICTACTOE:
+        ttt_device = self.game is TICTACTOE and os.environ.get("DIEE_ARENA") == "device"
+        if ttt_device:                                                          # one engine call (diee_ttt_arena): the same result
+            from .versus import play_tictactoe_device as play
+            self.log(f"DIEE_ARENA=device: the arena is one diee_ttt_arena call, option search = {self.engine.get_option('search')}")
+        elif self.game is TICTACTOE:
             from .versus import play_tictactoe as play
         elif os.environ.get("DIEE_ARENA") == "device":                          # every round on the device (diee_arena): the same result
             from .versus import play_device as play
@@ -596,6 +600,9 @@ class AlphaZero:
             return "saved-as-best"
         other = Engine(self.engine.device, self.game.game_id)
         other.load_weights(np.load(best))
+        if ttt_device:                                                          # the device arena wants both engines on the same options
+            for key in ("nn", "search"):
+                other.set_option(key, self.engine.get_option(key))
         res = play(Player(Agent.MODEL, self.engine), Player(Agent.MODEL, other), self.mcts_config,
                    self.config.temperature, seed=self.seed + 77 * self.calls, num_games=n_games)
         other.close()

@@ -115,7 +115,13 @@ def main_tictactoe(args):
             m1 = engine()
         if a2 == Agent.MCTS and m2 is None:
             m2 = engine()
-        print(play_tictactoe(Player(a1, m1), Player(a2, m2), mcts_config_from(conf), float(conf["temperature"])))
+        play = play_tictactoe
+        if os.environ.get("DIEE_ARENA") == "device":                                          # opt-in: one engine call (diee_ttt_arena): the same result
+            from .versus import play_tictactoe_device as play
+            print(f"[die-e_amd] DIEE_ARENA=device: the arena is one diee_ttt_arena call, option search = {eng.get_option('search')}"
+                  " (DIEE_TTT_SEARCH=device puts every round on the GPU)")
+        print(play(Player(a1, m1), Player(a2, m2), mcts_config_from(conf), float(conf["temperature"]),
+                   **({"engine": eng} if play is not play_tictactoe else {})))
     return 0
 
 

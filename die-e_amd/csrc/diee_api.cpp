@@ -307,6 +307,18 @@ diee_status diee_arena_ex(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2, ui
     API_END(c)
 }
 
+diee_status diee_ttt_arena(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2, uint32_t n_games, const diee_mcts_cfg* cfg, float temperature,
+                           uint64_t seed, uint32_t round_limit, uint32_t max_rounds, const uint32_t flags[2], diee_arena_result* res, int8_t* winner,
+                           uint32_t* retired_round, int8_t* retired_side, diee_ttt_state* final_states, diee_stats* stats) {
+    diee_ctx* c = p1 ? p1 : p2;                                  // the ctx that hosts the call (its option "search", stream, buffers, error text)
+    API_BEGIN(c)
+    if ((p1 && !p1->ttt) || (p2 && !p2->ttt)) throw EngineError(DIEE_ERR_UNSUPPORTED, "this entry point needs tic-tac-toe ctxs (a backgammon ctx: diee_arena)");
+    if (!cfg || !flags) throw EngineError(DIEE_ERR_ARG, "null pointer");
+    c->ttt->arena(p1 ? p1->ttt : nullptr, agent1, p2 ? p2->ttt : nullptr, agent2, n_games, *cfg, temperature, seed, round_limit, max_rounds, flags, res,
+                  winner, retired_round, retired_side, final_states, stats);
+    API_END(c)
+}
+
 void diee_free_arena_log(diee_arena_log* l) {
     if (!l) return;
     free(l->owner);                                              // one block: first[], then the turns

@@ -15,6 +15,7 @@
 #include "bg_device.h"
 #include "engine.h"
 #include "search_host.h"
+#include "ttt_arena_device.h"
 #include "ttt_device.h"
 #include "ttt_search_device.h"
 #include "ttt_vanilla_device.h"
@@ -110,11 +111,12 @@ namespace {
 
 void Engine::set_option(const std::string& key, const std::string& value) {
     if (key == "search") {
-        if (value == "host") { dsearch_.reset(); dvanilla_.reset(); return; }
+        if (value == "host") { darena_.reset(); dsearch_.reset(); dvanilla_.reset(); return; }
         if (value != "device") throw EngineError(DIEE_ERR_ARG, "option search: `" + value + "` is neither `host` nor `device`");
         if (!dev_) throw EngineError(DIEE_ERR_ARG, "option search = device needs option nn = device: the device search evaluates the device network");
         if (!dvanilla_) dvanilla_.reset(new DeviceVanilla(*dev_));
         if (!dsearch_) dsearch_.reset(new DeviceSearch(*dev_));              // buffers come with the first search
+        if (!darena_) darena_.reset(new DeviceArena(*dev_, *dsearch_, *dvanilla_));
         return;
     }
     if (key != "nn") unsupported_option(key);
@@ -156,7 +158,7 @@ void Engine::load_weights(const float* blob, size_t n) {
     w_.assign(blob, blob + n);
     // a failed upload must not leave "device" answering with the previous network: the ctx falls back to "host" (which holds the new
     // weights, and the host search with it) and the caller gets the HIP error, as in set_option
-    if (dev_) { try { upload(); } catch (...) { dsearch_.reset(); dvanilla_.reset(); dev_.reset(); throw; } }
+    if (dev_) { try { upload(); } catch (...) { darena_.reset(); dsearch_.reset(); dvanilla_.reset(); dev_.reset(); throw; } }
 }
 
 // ---- the network, fp32 ------------------------------------------------------------------------------------------------
@@ -572,6 +574,118 @@ void Engine::mcts_vanilla_batch(const diee_ttt_state* roots, uint32_t n, const d
         }
     }
     if (stats) { *stats = st; stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+}
+
+// ---- the arena: play() / get_actions_for_player (versus.rs:160-318) for TicTacToe -------------------------------------------------------------
+void Engine::arena(const Engine* e1, int agent1, const Engine* e2, int agent2, uint32_t n_games, const diee_mcts_cfg& cfg, float temperature,
+                   uint64_t seed, uint32_t round_limit, uint32_t max_rounds, const uint32_t flags[2], diee_arena_result* res, int8_t* winner,
+                   uint32_t* retired_round, int8_t* retired_side, diee_ttt_state* final_states, diee_stats* stats) const {
+    if (res) memset(res, 0, sizeof *res);
+    if (stats) memset(stats, 0, 2 * sizeof(diee_stats));
+    if (n_games == 0 || round_limit == 0) throw EngineError(DIEE_ERR_ARG, "the arena needs n_games >= 1 and round_limit >= 1");
+    if (n_games > (1u << 22)) throw EngineError(DIEE_ERR_ARG, "too many games in flight");
+    const Engine* const eng[2] = {e1, e2};
+    const int agents[2] = {agent1, agent2};
+    bool any_mcts = false;
+    for (int s = 0; s < 2; ++s) {
+        if (agents[s] != DIEE_AGENT_RANDOM && agents[s] != DIEE_AGENT_MODEL && agents[s] != DIEE_AGENT_MCTS)
+            throw EngineError(DIEE_ERR_ARG, "agent: DIEE_AGENT_RANDOM, DIEE_AGENT_MODEL or DIEE_AGENT_MCTS");
+        if (agents[s] == DIEE_AGENT_MODEL && !eng[s]) throw EngineError(DIEE_ERR_ARG, "a Model agent needs its ctx");
+        if (agents[s] == DIEE_AGENT_MODEL && !eng[s]->loaded()) throw EngineError(DIEE_ERR_NO_WEIGHTS, "diee_load_weights has not been called for a Model agent's ctx");
+        any_mcts = any_mcts || agents[s] == DIEE_AGENT_MCTS;
+    }
+    if (any_mcts) vanilla_check_cfg(cfg);
+    if (darena_) {
+        ArenaArgs a{};
+        for (int s = 0; s < 2; ++s) {
+            if (eng[s] && (!eng[s]->dsearch_ || eng[s]->device_ != device_))
+                throw EngineError(DIEE_ERR_ARG, "the device arena needs every ctx of the call on option search = device and on the hosting ctx's GPU");
+            a.agents[s] = agents[s]; a.flags[s] = flags[s];
+            a.nets[s] = agents[s] == DIEE_AGENT_MODEL ? &eng[s]->dev_->params() : nullptr;
+        }
+        a.n_games = n_games; a.cfg = cfg; a.temperature = temperature; a.seed = seed; a.round_limit = round_limit; a.max_rounds = max_rounds;
+        darena_->run(a, res, winner, retired_round, retired_side, final_states, stats);
+        return;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const float inv_t = (float)(1.0 / (double)temperature);                                // :283 pow_(1.0 / temp)
+    std::vector<diee_ttt_state> states(n_games), roots;
+    std::vector<int8_t> win(n_games, 0), rside(n_games, -1);
+    std::vector<uint32_t> rround(n_games, 0xFFFFFFFFu), ids, rounds;
+    std::vector<uint8_t> moves;
+    for (uint32_t g = 0; g < n_games; ++g) { memset(&states[g], 0, sizeof states[g]); states[g].player = g < n_games / 2 ? -1 : 1; }     // :172-174
+    diee_stats st[2];
+    memset(st, 0, sizeof st);
+    diee_arena_result r{};
+    RootResult R;
+    uint32_t round = 0;
+    for (;;) {                                                                             // :191
+        std::vector<uint32_t> lists[2];                                                    // :195-196, ascending game index
+        for (uint32_t g = 0; g < n_games; ++g) if (rround[g] == 0xFFFFFFFFu) lists[states[g].player == -1 ? 0 : 1].push_back(g);
+        if (lists[0].empty() && lists[1].empty()) break;
+        if (max_rounds != 0 && round >= max_rounds) break;
+        for (int s = 0; s < 2; ++s) {
+            ids = lists[s];
+            const uint32_t n = (uint32_t)ids.size();
+            if (!n) continue;
+            roots.clear();
+            for (uint32_t g : ids) roots.push_back(states[g]);
+            rounds.assign(n, round);
+            moves.assign(n, 10);                                                           // TicTacToe::EMPTY_MOVE
+            const bool quirks = (flags[s] & DIEE_FLAG_REF_QUIRKS) != 0;
+            if (agents[s] == DIEE_AGENT_MODEL) {                                           // :279-299
+                eng[s]->search(roots.data(), n, cfg, seed, 2 * round + (uint32_t)s, quirks, &st[s], R);
+                st[s].move_steps += 1;
+                for (uint32_t k = 0; k < n; ++k) {
+                    float row[A];
+                    double total = 0.0;
+                    for (int c = 0; c < A; ++c) {
+                        const float x = R.probs[(size_t)k * A + c];
+                        row[c] = det_powf(x > 0.f ? x : 0.f, inv_t);                       // (NaN, the row of a childless root: 0)
+                        total += (double)row[c];
+                    }
+                    if (R.n_children[k] != 0 && total > 0.0)                               // :286-293: else EMPTY_MOVE
+                        moves[k] = (uint8_t)weighted_select(row, draw_uniform(seed, ids[k], round, kTagSample, 0u));
+                }
+            } else if (agents[s] == DIEE_AGENT_MCTS) {                                     // :303-306
+                diee_vanilla_stats vs;
+                (eng[s] ? eng[s] : this)->mcts_vanilla_batch(roots.data(), n, cfg, seed, ids.data(), rounds.data(), flags[s], moves.data(), nullptr, nullptr,
+                                                             nullptr, &vs);
+                st[s].move_steps += 1;
+                st[s].selections += vs.iterations; st[s].expansions += vs.expansions; st[s].terminal_hits += vs.terminal_hits; st[s].depth_sum += vs.depth_sum;
+            } else {                                                                       // :308-317
+                for (uint32_t k = 0; k < n; ++k) {
+                    uint8_t mv[9];
+                    const int count = valid_moves(roots[k], mv);
+                    if (!count) continue;
+                    const int idx = (int)(draw_uniform(seed, ids[k], round, kTagSample, 0u) * (double)count);
+                    moves[k] = mv[idx > count - 1 ? count - 1 : idx];
+                }
+            }
+            for (uint32_t k = 0; k < n; ++k) {                                             // :220-266
+                const uint32_t g = ids[k];
+                st[s].plies += 1;
+                if (moves[k] > 8) { skip_turn(states[g]); continue; }                      // :225-228: no winner / round-limit check
+                apply_move(states[g], moves[k]);                                           // :230
+                st[s].fragments += 1;
+                int w = 0;
+                if (!check_winner(states[g], w) && round + 1 < round_limit) continue;      // :233-237 (round_count was incremented at :219)
+                win[g] = (int8_t)w; rround[g] = round; rside[g] = (int8_t)s;
+                st[s].games += 1;
+                (w < 0 ? r.wins_p1 : w > 0 ? r.wins_p2 : r.draws) += 1;
+            }
+        }
+        ++round;                                                                           // :219
+    }
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int s = 0; s < 2; ++s) { st[s].nn_rows = st[s].nn_evals; st[s].seconds = secs; }
+    r.rounds = round; r.seconds = secs;
+    if (winner) memcpy(winner, win.data(), n_games);
+    if (retired_round) memcpy(retired_round, rround.data(), (size_t)n_games * sizeof(uint32_t));
+    if (retired_side) memcpy(retired_side, rside.data(), n_games);
+    if (final_states) memcpy(final_states, states.data(), (size_t)n_games * sizeof(diee_ttt_state));
+    if (stats) memcpy(stats, st, sizeof st);
+    if (res) *res = r;
 }
 
 }  // namespace ttt

@@ -12,6 +12,7 @@
 // forward() to one launch of k_ttt_net (ttt_device.h); rules, search and driver stay here.  Over that, option "search" = "device" (opt-in
 // too) runs the batched search as one launch of k_ttt_search per iteration (ttt_search_device.h); the driver stays here.
 // Agent::Mcts (mcts_vanilla_batch, no network) follows option "search" too: here by default, k_ttt_vanilla (ttt_vanilla_device.h) on "device".
+// So does the arena that plays those searches against each other (arena): a round loop here, every round on the device (ttt_arena_device.h) on "device".
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -41,6 +42,7 @@ struct Conv { std::vector<float> w, b; int cout = 0, cin = 0; };          // OIH
 class DeviceNet;                                                          // ttt_device.h
 class DeviceSearch;                                                       // ttt_search_device.h
 class DeviceVanilla;                                                      // ttt_vanilla_device.h
+class DeviceArena;                                                        // ttt_arena_device.h
 
 // what a search leaves for its callers: get_prob_tensor_parallel's rows (utils.rs:42-58) and the roots' counts
 struct RootResult {
@@ -75,6 +77,12 @@ public:
     void mcts_vanilla_batch(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, const uint32_t* game_ids,
                             const uint32_t* rounds, uint32_t flags, uint8_t* moves, uint32_t* n_children, float* child_visits,
                             float* child_values, diee_vanilla_stats* stats) const;
+    // play::<TicTacToe> (versus.rs:160-318): diee_ttt_arena of include/diee.h, called on the hosting ctx (e1, or e2 when e1 is null).  Option
+    // "search" of the hosting ctx names the path: "host" = the round loop of ttt_host.cpp over each player's own searches, "device" = every round
+    // on this ctx's stream (ttt_arena_device.h).
+    void arena(const Engine* e1, int agent1, const Engine* e2, int agent2, uint32_t n_games, const diee_mcts_cfg& cfg, float temperature, uint64_t seed,
+               uint32_t round_limit, uint32_t max_rounds, const uint32_t flags[2], diee_arena_result* res, int8_t* winner, uint32_t* retired_round,
+               int8_t* retired_side, diee_ttt_state* final_states, diee_stats* stats) const;
 
 private:
     void upload() const;                                                    // the folded weights -> dev_
@@ -85,6 +93,7 @@ private:
     std::unique_ptr<DeviceNet> dev_;                                        // non-null = "nn" is "device"
     std::unique_ptr<DeviceSearch> dsearch_;                                 // non-null = "search" is "device" (dev_ is non-null then; declared after it: destroyed first)
     std::unique_ptr<DeviceVanilla> dvanilla_;                               // set and cleared with dsearch_
+    std::unique_ptr<DeviceArena> darena_;                                   // set and cleared with dsearch_; it drives the two above (destroyed before them)
     Conv init_, c1_[BLOCKS], c2_[BLOCKS], pconv_, vconv_;
     std::vector<float> pfc_w_, pfc_b_, vfc_w_, vfc_b_;
     std::vector<float> w_;                                                  // the blob as loaded (non-empty = loaded)

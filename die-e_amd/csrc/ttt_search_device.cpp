@@ -37,6 +37,7 @@ void DeviceSearch::release() {
 // A buffer that has to grow is freed first and its capacity cleared, so a failed allocation leaves the ctx consistent (the next call
 // allocates again) and the error goes to the caller before anything has been launched.
 void DeviceSearch::reserve(uint32_t n, uint32_t iterations) {
+    if (iterations > (0x7FFFFFFFu - 10u) / 8u) throw EngineError(DIEE_ERR_CAPACITY, "option search = device: a game's nodes are indexed with 31 bits");
     const size_t slab = 10 + 8 * (size_t)iterations, nodes = (size_t)n * slab;
     const size_t out = kCntCount * sizeof(unsigned long long) + (2 * (size_t)iterations + (size_t)n * (A + 2)) * 4;
     if (n <= cap_n_ && nodes <= cap_nodes_ && out <= cap_out_) return;
@@ -78,42 +79,18 @@ void DeviceSearch::run(const diee_ttt_state* roots, uint32_t n, const diee_mcts_
         for (int cidx = 0; cidx < 9; ++cidx) ok = ok && roots[i].board[cidx] >= -1 && roots[i].board[cidx] <= 1;
         if (!ok) throw EngineError(DIEE_ERR_ARG, "option search = device: root " + std::to_string(i) + " has a cell or a player outside -1 / 0 / +1");
     }
-    if (cfg.iterations > (0x7FFFFFFFu - 10u) / 8u) throw EngineError(DIEE_ERR_CAPACITY, "option search = device: a game's nodes are indexed with 31 bits");
     HIPCHK(hipSetDevice(net_.device()));
     try { reserve(n, cfg.iterations); } catch (...) { (void)hipGetLastError(); throw; }      // (a failed allocation is not the next launch's error)
     hipStream_t stream = net_.stream();
 
-    SearchParams P{};
-    P.net = net_.params();
-    P.roots = (const diee_ttt_state*)d_roots_;
-    P.nodes = (SearchNode*)d_nodes_;
-    P.games = (SearchGame*)d_games_;
-    unsigned char* o = (unsigned char*)d_out_;
-    const size_t head = kCntCount * sizeof(unsigned long long) + 2 * (size_t)cfg.iterations * 4;     // counters and per-iteration words: cleared in-stream
-    P.counters = (unsigned long long*)o;
-    P.any_selected = (uint32_t*)(o + kCntCount * sizeof(unsigned long long));
-    P.never_selected = P.any_selected + cfg.iterations;
-    P.probs = (float*)(o + head);
-    P.n_children = (uint32_t*)(P.probs + (size_t)n * A);
-    P.root_visits = (float*)(P.n_children + n);
-    P.n = n; P.iterations = cfg.iterations; P.slab = 10 + 8 * cfg.iterations; P.quirks = quirks ? 1u : 0u;
-    P.c = cfg.c; P.eps = cfg.dir_eps; P.one_minus_eps = 1.0f - cfg.dir_eps;
-    dirichlet_host(seed, step, cfg.dir_alpha, A, P.noise);                                       // apply_dirichlet, noise.rs:27-34: ONE sample for all rows
-
     memcpy(h_roots_, roots, (size_t)n * sizeof(diee_ttt_state));
     HIPCHK(hipMemcpyAsync(d_roots_, h_roots_, (size_t)n * sizeof(diee_ttt_state), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemsetAsync(d_out_, 0, head, stream));
-    for (uint32_t k = 0; k <= cfg.iterations; ++k) {
-        P.k = k;
-        launch_ttt_search(stream, P);
-        HIPCHK(hipGetLastError());
-    }
-    const size_t bytes = head + (size_t)n * (A + 2) * 4;
-    HIPCHK(hipMemcpyAsync(h_out_, d_out_, bytes, hipMemcpyDeviceToHost, stream));
+    const Enqueued E = enqueue((const diee_ttt_state*)d_roots_, n, net_.params(), cfg, seed, step, quirks);
+    HIPCHK(hipMemcpyAsync(h_out_, d_out_, E.bytes, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
 
     const unsigned char* h = (const unsigned char*)h_out_;
-    const float* probs = (const float*)(h + head);
+    const float* probs = (const float*)(h + E.head);
     const uint32_t* nch = (const uint32_t*)(probs + (size_t)n * A);
     const float* rv = (const float*)(nch + n);
     R.probs.assign(probs, probs + (size_t)n * A);
@@ -129,6 +106,36 @@ void DeviceSearch::run(const diee_ttt_state* roots, uint32_t n, const diee_mcts_
         if (cnt[kCntMaxChildren] > st->max_children) st->max_children = cnt[kCntMaxChildren];
         st->selections += cnt[kCntSelections]; st->depth_sum += cnt[kCntDepthSum]; st->terminal_hits += cnt[kCntTerminalHits];
     }
+}
+
+DeviceSearch::Enqueued DeviceSearch::enqueue(const diee_ttt_state* d_roots, uint32_t n, const NetParams& net, const diee_mcts_cfg& cfg, uint64_t seed,
+                                             uint32_t step, bool quirks) {
+    hipStream_t stream = net_.stream();
+
+    SearchParams P{};
+    P.net = net;
+    P.roots = d_roots;
+    P.nodes = (SearchNode*)d_nodes_;
+    P.games = (SearchGame*)d_games_;
+    unsigned char* o = (unsigned char*)d_out_;
+    const size_t head = kCntCount * sizeof(unsigned long long) + 2 * (size_t)cfg.iterations * 4;     // counters and per-iteration words: cleared in-stream
+    P.counters = (unsigned long long*)o;
+    P.any_selected = (uint32_t*)(o + kCntCount * sizeof(unsigned long long));
+    P.never_selected = P.any_selected + cfg.iterations;
+    P.probs = (float*)(o + head);
+    P.n_children = (uint32_t*)(P.probs + (size_t)n * A);
+    P.root_visits = (float*)(P.n_children + n);
+    P.n = n; P.iterations = cfg.iterations; P.slab = 10 + 8 * cfg.iterations; P.quirks = quirks ? 1u : 0u;
+    P.c = cfg.c; P.eps = cfg.dir_eps; P.one_minus_eps = 1.0f - cfg.dir_eps;
+    dirichlet_host(seed, step, cfg.dir_alpha, A, P.noise);                                       // apply_dirichlet, noise.rs:27-34: ONE sample for all rows
+
+    HIPCHK(hipMemsetAsync(d_out_, 0, head, stream));
+    for (uint32_t k = 0; k <= cfg.iterations; ++k) {
+        P.k = k;
+        launch_ttt_search(stream, P);
+        HIPCHK(hipGetLastError());
+    }
+    return Enqueued{P.counters, P.any_selected, P.probs, P.n_children, head, head + (size_t)n * (A + 2) * 4};
 }
 
 }  // namespace ttt

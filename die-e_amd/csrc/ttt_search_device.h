@@ -73,9 +73,21 @@ public:
     DeviceSearch& operator=(const DeviceSearch&) = delete;
     // the whole search; throws EngineError and writes nothing to R or st if a buffer cannot be had or a HIP call fails
     void run(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step, bool quirks, diee_stats* st, RootResult& R);
+    // What a search leaves on the device: pointers into d_out_, good until the next search is enqueued.
+    struct Enqueued {
+        const unsigned long long* counters;    // [kCntCount]
+        const uint32_t* any_selected;          // [iterations]
+        const float* probs;                    // [n][9]
+        const uint32_t* n_children;            // [n]
+        size_t head, bytes;                    // of d_out_: counters and flag words | all of it
+    };
+    // run() without its two ends: n >= 1 roots already on the device (cells of -1 / 0 / +1), launches 0 .. iterations enqueued on the ctx's
+    // stream over `net` (this ctx's network, or another ctx's on the same device: read-only), nothing copied and nothing waited for.
+    // The caller has reserved (n or more games, cfg.iterations) and set the device.
+    Enqueued enqueue(const diee_ttt_state* d_roots, uint32_t n, const NetParams& net, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step, bool quirks);
+    void reserve(uint32_t n, uint32_t iterations);
 
 private:
-    void reserve(uint32_t n, uint32_t iterations);
     void release();
     DeviceNet& net_;
     void *d_roots_ = nullptr, *d_nodes_ = nullptr, *d_games_ = nullptr, *d_out_ = nullptr, *h_roots_ = nullptr, *h_out_ = nullptr;

@@ -32,41 +32,13 @@
 #include <hip/hip_runtime.h>
 
 #include "ttt_net_device.h"
+#include "ttt_rules_device.h"
 #include "ttt_search_device.h"
 
 namespace diee {
 namespace ttt {
 
 namespace {
-#define DIEE_TTT_FN __device__ __forceinline__ DIEE_TTT_NO_PK_F32
-
-DIEE_TTT_FN int cell_of(uint32_t st, int j) { return (int)(st << (30 - 2 * j)) >> 30; }                 // -1 / 0 / +1
-DIEE_TTT_FN int player_of(uint32_t st) { return (st >> 18) & 1u ? 1 : -1; }
-DIEE_TTT_FN uint32_t pack_cell(int v, int j) { return ((uint32_t)v & 3u) << (2 * j); }
-DIEE_TTT_FN uint32_t empty_cells(uint32_t st) {                                                      // bit j: cell j is empty
-    uint32_t m = 0;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) m |= ((st >> (2 * j)) & 3u) == 0u ? 1u << j : 0u;
-    return m;
-}
-__device__ __forceinline__ constexpr int line_cell(int l, int i) { return l < 3 ? 3 * l + i : l < 6 ? l - 3 + 3 * i : l == 6 ? 4 * i : 2 + 2 * i; }
-// check_winner (mod.rs:60-81): the first complete line in the order rows, columns, 0-4-8, 2-4-6; else a full board is a draw
-DIEE_TTT_FN bool finished(uint32_t st, int& winner) {
-    bool found = false;
-    winner = 0;
-#pragma unroll
-    for (int l = 0; l < 8; ++l) {
-        const int a = cell_of(st, line_cell(l, 0));
-        if (!found && a != 0 && a == cell_of(st, line_cell(l, 1)) && a == cell_of(st, line_cell(l, 2))) { winner = a; found = true; }
-    }
-    return found || (st & 0x15555u) == 0x15555u;
-}
-
-DIEE_TTT_FN float as_f32(uint32_t u) { return __builtin_bit_cast(float, u); }      // by value: a vector element is no operand for the builtin
-DIEE_TTT_FN uint32_t row_get(uint32_t v, int src_lane) { return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v); }
-DIEE_TTT_FN float row_getf(float v, int src_lane) { return as_f32(row_get(__builtin_bit_cast(uint32_t, v), src_lane)); }
-DIEE_TTT_FN uint32_t row_ballot(bool p, int row0) { return (uint32_t)(__builtin_amdgcn_ballot_w64(p) >> row0) & 0xFFFFu; }
-
 // Node::alpha_ucb, node.rs:98-112 = ucb() of ttt_host.cpp, f32 in this association (sq = sqrt(visits of the parent))
 DIEE_TTT_FN float puct(float n, float val, float prior, float sq, float c) {
     const float q = n == 0.f ? 0.f : val / n;

@@ -78,9 +78,7 @@ const VanillaOut* DeviceVanilla::run(const diee_ttt_state* roots, uint32_t n, co
                                      const uint32_t* rounds, bool quirks) {
     if (n == 0) return nullptr;
     HIPCHK(hipSetDevice(net_.device()));
-    const uint32_t slab = cfg.iterations + 1 < kVanillaMaxNodes ? cfg.iterations + 1 : kVanillaMaxNodes;
-    const bool lds = slab <= kVanillaLdsNodes;
-    try { reserve(n, lds ? 0 : (size_t)n * slab * kVNodeWords, cfg.iterations + 2); } catch (...) { (void)hipGetLastError(); throw; }
+    reserve_for(n, cfg);
     hipStream_t stream = net_.stream();
 
     diee_ttt_state* h_roots = (diee_ttt_state*)h_in_;
@@ -89,10 +87,34 @@ const VanillaOut* DeviceVanilla::run(const diee_ttt_state* roots, uint32_t n, co
     for (uint32_t i = 0; i < n; ++i) { h_keys[2 * i] = game_ids ? game_ids[i] : i; h_keys[2 * i + 1] = rounds ? rounds[i] : 0u; }
     const size_t in = (size_t)n * (sizeof(diee_ttt_state) + 2 * sizeof(uint32_t));
     HIPCHK(hipMemcpyAsync(d_in_, h_in_, in, hipMemcpyHostToDevice, stream));
+    const diee_ttt_state* d_roots = (const diee_ttt_state*)d_in_;
+    (void)enqueue(d_roots, (const uint32_t*)(d_roots + n), n, cfg, seed, quirks);
+    HIPCHK(hipMemcpyAsync(h_out_, d_out_, (size_t)n * sizeof(VanillaOut), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const VanillaOut* out = (const VanillaOut*)h_out_;
+    for (uint32_t i = 0; i < n; ++i)
+        if (out[i].overflow) throw EngineError(DIEE_ERR_CAPACITY, "k_ttt_vanilla: a game's slab is full");
+    return out;
+}
+
+namespace {
+uint32_t slab_of(const diee_mcts_cfg& cfg) { return cfg.iterations + 1 < kVanillaMaxNodes ? cfg.iterations + 1 : kVanillaMaxNodes; }
+}  // namespace
+
+void DeviceVanilla::reserve_for(uint32_t n, const diee_mcts_cfg& cfg) {
+    const uint32_t slab = slab_of(cfg);
+    try { reserve(n, slab <= kVanillaLdsNodes ? 0 : (size_t)n * slab * kVNodeWords, cfg.iterations + 2); } catch (...) { (void)hipGetLastError(); throw; }
+}
+
+const VanillaOut* DeviceVanilla::enqueue(const diee_ttt_state* d_roots, const uint32_t* d_keys, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed,
+                                         bool quirks) {
+    const uint32_t slab = slab_of(cfg);
+    const bool lds = slab <= kVanillaLdsNodes;
+    hipStream_t stream = net_.stream();
 
     VanillaParams P{};
-    P.roots = (const diee_ttt_state*)d_in_;
-    P.keys = (const uint32_t*)(P.roots + n);
+    P.roots = d_roots;
+    P.keys = d_keys;
     P.ln = (const float*)d_ln_;
     P.nodes = lds ? nullptr : (uint32_t*)d_nodes_;
     P.games = (VanillaGame*)d_games_;
@@ -110,12 +132,7 @@ const VanillaOut* DeviceVanilla::run(const diee_ttt_state* roots, uint32_t n, co
         HIPCHK(hipGetLastError());
         it = P.it1;
     } while (it < cfg.iterations);
-    HIPCHK(hipMemcpyAsync(h_out_, d_out_, (size_t)n * sizeof(VanillaOut), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    const VanillaOut* out = (const VanillaOut*)h_out_;
-    for (uint32_t i = 0; i < n; ++i)
-        if (out[i].overflow) throw EngineError(DIEE_ERR_CAPACITY, "k_ttt_vanilla: a game's slab is full");
-    return out;
+    return (const VanillaOut*)d_out_;
 }
 
 }  // namespace ttt

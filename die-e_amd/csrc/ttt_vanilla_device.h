@@ -77,6 +77,11 @@ public:
     // anything is written if a buffer cannot be had or a HIP call fails.
     const VanillaOut* run(const diee_ttt_state* roots, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, const uint32_t* game_ids,
                           const uint32_t* rounds, bool quirks);
+    // run() without its two ends: n >= 1 roots and their keys [n][2] already on the device, the launches enqueued on the ctx's stream, nothing
+    // copied and nothing waited for.  -> the answers [n] on the device, good until the next search is enqueued (`overflow` is the reader's to
+    // check).  The caller has called reserve_for (n or more games, the same cfg) and set the device.
+    const VanillaOut* enqueue(const diee_ttt_state* d_roots, const uint32_t* d_keys, uint32_t n, const diee_mcts_cfg& cfg, uint64_t seed, bool quirks);
+    void reserve_for(uint32_t n, const diee_mcts_cfg& cfg);
 
 private:
     void reserve(uint32_t n, size_t node_words, uint32_t ln_n);

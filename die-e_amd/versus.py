@@ -6,7 +6,8 @@ Q22); DIEE_VANILLA_ROLLOUTS=1 (or vanilla_rollouts=True) turns the quirk off -- 
 
 `play` is written against a small backend interface so that the same driver can run on the engine or,
 in the parity tests, on the CPU oracle.  `play_device` is the same arena as ONE engine call (diee_arena): every round
-on the device, the same games bit for bit (Model, Mcts and Random agents); DIEE_ARENA=device makes the callers use it.
+on the device, the same games bit for bit (Model, Mcts and Random agents); DIEE_ARENA=device makes the callers use it.  `play_tictactoe` / `play_tictactoe_device`
+(diee_ttt_arena) are the same pair for tic-tac-toe.
 
 The reference declares Turn { roll, action, player } and Game.turns, and print_game walks them, but play() never pushes one (Q21).
 record_turns=True (DIEE_RECORD_TURNS=1 for `diee.py play`) is the replay as it was meant -- opt-in and logged: both drivers record
@@ -562,6 +563,29 @@ def play_tictactoe(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_gam
     res = PlayResult(player1.player_type, player2.player_type, int(wins_p1), int(wins_p2), num_games, [])
     res.final_states = states
     res.rounds = round_count
+    return res
+
+
+def play_tictactoe_device(player1, player2, mcts_config, temp, seed=0xD1EE0001, num_games=400, round_limit=400, max_rounds=0, engine=None,
+                          vanilla_rollouts=None):
+    """play_tictactoe() as ONE engine call (Engine.ttt_arena, diee_ttt_arena): the same PlayResult -- wins, final_states, rounds.  With
+    option "search" = "device" on the players' engines every round runs on the GPU; otherwise the round loop runs in the engine on the
+    host.  `engine` hosts a call none of whose players brings one.  The flags are what play_tictactoe searches with: the quirks for a
+    Model agent, `not vanilla_rollouts` for an Mcts agent."""
+    from . import AGENT_MCTS, AGENT_MODEL, AGENT_RANDOM, FLAG_REF_QUIRKS, ttt_arena
+    kinds = {Agent.MODEL: AGENT_MODEL, Agent.RANDOM: AGENT_RANDOM, Agent.MCTS: AGENT_MCTS}
+    types = (player1.player_type, player2.player_type)
+    if vanilla_rollouts is None:
+        vanilla_rollouts = Agent.MCTS in types and vanilla_rollouts_from_env()
+    flags = [0 if (vanilla_rollouts and t == Agent.MCTS) else FLAG_REF_QUIRKS for t in types]
+    e1, e2 = player1.model, player2.model
+    if e1 is None and e2 is None:
+        e1 = engine
+    r = ttt_arena(e1, kinds[types[0]], e2, kinds[types[1]], num_games, mcts_config, temp, seed, round_limit, max_rounds, flags)
+    res = PlayResult(types[0], types[1], r["wins_p1"], r["wins_p2"], num_games, [])
+    res.final_states = r["final_states"]
+    res.rounds = r["rounds"]
+    res.device = r                             # the call's per-game outputs and per-player stats
     return res
 
 

@@ -65,7 +65,7 @@ typedef struct {
  * a ctx created with DIEE_GAME_TTT runs rules, the 64-filter 4-block ResNet (mod.rs:20-24), the search and the
  * self-play driver in C++ on the HOST (die-e_amd/csrc/ttt_host.cpp) and needs no GPU; its states are diee_ttt_state
  * records (cast the pointer where a prototype says diee_bg_state), policies / ps rows have 9 entries, planes 27.
- * Served for such a ctx: diee_load_weights, diee_nn_forward, diee_mcts_batch, diee_ttt_mcts_vanilla_batch, diee_self_play (+ lifetime /
+ * Served for such a ctx: diee_load_weights, diee_nn_forward, diee_mcts_batch, diee_ttt_mcts_vanilla_batch, diee_ttt_arena, diee_self_play (+ lifetime /
  * error calls) and the two options "nn" and "search" (below); everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no
  * host path. */
 typedef struct {
@@ -487,6 +487,40 @@ diee_status diee_arena_ex(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2,
                           diee_arena_result* res, int8_t* winner, uint32_t* retired_round, int8_t* retired_side,
                           diee_bg_state* initial_states, diee_bg_state* final_states, diee_stats* stats);
 void        diee_free_arena_log(diee_arena_log* log);
+
+/* ---- the arena for TIC-TAC-TOE: play::<TicTacToe> (versus.rs:160-318 is generic over LearnableGame) -- n_games games between two agents in ONE
+ * call, for tic-tac-toe ctxs (diee_arena / diee_arena_ex keep refusing them; a backgammon ctx here: DIEE_ERR_UNSUPPORTED).
+ *   Game i starts from the empty board, side -1 ("player 1") to move for i < n_games / 2, side +1 for the rest (:172-174).  Each round the live
+ *   games are split by side to move, stable, in ascending game index; a side without games does nothing that round.
+ *   DIEE_AGENT_MODEL: the side's list is searched as diee_mcts_batch searches it, with step = 2 * round + side (side 0 = player 1) and
+ *   flags[side].  A game's row = its visit probabilities with NaN read as 0; entries > 0 are raised to (float)(1 / temperature) by the engine's
+ *   deterministic powf (what diee_self_play uses).  A root without children or an all-zero row skips the turn (all terms are >= 0: "the sum is
+ *   0" does not depend on the order of the sum).  Otherwise the move is the first cell whose sequential f64 running sum exceeds u * total, u =
+ *   the uniform of (seed, i, round, TAG_SAMPLE); if rounding leaves none, the last non-zero cell.
+ *   DIEE_AGENT_RANDOM: empties[min(int(u * count), count - 1)] of the empty cells in ascending order, the same u.
+ *   DIEE_AGENT_MCTS: the answer of diee_ttt_mcts_vanilla_batch with game_ids = i, rounds = round and flags[side]; 10 skips the turn.
+ *   `temperature` is not used by the last two, and their ctx may be NULL as long as the other one is not (then that one hosts the call).
+ *   A skipped turn flips the player and is checked neither for a winner nor for the round limit (:225-228).  An applied move is followed by
+ *   check_winner; with no winner and round + 1 >= round_limit the game retires as a draw (:233-237).
+ * max_rounds, winner, retired_round, retired_side and res as in diee_arena (res->illegal_decodes stays 0: every move is an empty cell by
+ * construction); final_states [n_games] or NULL.
+ * stats[2], per player, or NULL: the search counters of that player's searches (a Model agent: nn_evals = nn_rows, expansions, children,
+ * max_children, selections, depth_sum, terminal_hits; an Mcts agent: selections (= iterations), expansions, terminal_hits, depth_sum);
+ * move_steps = its searches; plies = the turns it took, skipped ones included; fragments = the turns in which a move was applied; games = games
+ * retired by one of its moves; seconds = the call's wall clock.  band_launches, tail_* and the timing fields stay 0.
+ * The call follows option "search" of the hosting ctx (p1, or p2 when p1 is NULL), as diee_ttt_mcts_vanilla_batch does; both paths give the
+ * same bits.  "host" (default): a round loop on the host over each player's own searches, wherever its ctx runs them.  "device": every round on
+ * the hosting ctx's stream -- the split by side, both searches (k_ttt_search, k_ttt_vanilla; player 2's over p2's network, which is only read),
+ * the sampling, the moves and the totals; the host reads three words per round (the two sides' counts and the games alive) and the results
+ * once.  Then every non-NULL ctx of the call must be on "search" = "device" and on the same GPU, else DIEE_ERR_ARG; a ctx without weights can be
+ * (Random and Mcts players).
+ * A Model agent whose ctx is NULL: DIEE_ERR_ARG, without loaded weights: DIEE_ERR_NO_WEIGHTS; n_games == 0, round_limit == 0, both ctxs NULL, cfg
+ * or flags NULL: DIEE_ERR_ARG; an Mcts agent's cfg as for diee_ttt_mcts_vanilla_batch. */
+diee_status diee_ttt_arena(diee_ctx* p1, int agent1, diee_ctx* p2, int agent2, uint32_t n_games,
+                           const diee_mcts_cfg* cfg, float temperature, uint64_t seed,
+                           uint32_t round_limit, uint32_t max_rounds, const uint32_t* flags /* [2], per player */,
+                           diee_arena_result* res, int8_t* winner, uint32_t* retired_round,
+                           int8_t* retired_side, diee_ttt_state* final_states, diee_stats* stats /*[2]*/);
 
 /* ---- training-step kernels (no ctx: plain device pointers of the caller's framework, launched on `stream`, a
  * hipStream_t; NULL = the default stream).  AlphaZero::train (alphazero.rs:202-261) is tch autograd in the reference;

@@ -1,0 +1,68 @@
+"""Tic-tac-toe arena: the Python driver versus.play_tictactoe against ONE engine call, versus.play_tictactoe_device (diee_ttt_arena), both over
+the same two search = device engines of one GPU.
+
+    python scripts/ttt_arena_bench.py [--out FILE] [--reps 20]
+
+Model against Model (two weight blobs), 50 iterations, at 16 and 400 games.  The searches are the same launches on both sides; what differs is
+who runs a round between them -- Python (a copy-out and a synchronise per search, np.power, weighted_select and the rules per game) or
+k_ttt_arena_split / k_ttt_arena_move (three words per round).  Temperature 1.0, where both drivers sample from the same rows, so every
+timed pair is also checked to have played the same games.  Every call is synchronous on return, so a host clock around it is a call time.
+Each row is warmed up on both drivers, the two alternate rep by rep; the table gives the median and the spread, and a difference counts only
+if it exceeds that spread.  Prints a markdown table and, last, one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import diee_amd  # noqa: E402
+from diee_amd import versus  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out"); ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    engines = []
+    for seed in (0, 1):
+        e = diee_amd.Engine(0, diee_amd.GAME_TTT)
+        e.load_weights(diee_amd.random_weights(seed, diee_amd.GAME_TTT))
+        engines.append(e.set_option("nn", "device").set_option("search", "device"))
+    players = [versus.Player(versus.Agent.MODEL, e) for e in engines]
+    cfg = diee_amd.MctsConfig(iterations=50, c=2.0, round_limit=400, dir_alpha=0.3, dir_eps=0.25)
+    drivers = {"python": versus.play_tictactoe, "device": versus.play_tictactoe_device}
+
+    rows = []
+    for n in (16, 400):
+        t = {k: [] for k in drivers}
+        for i in range(a.reps + 2):                                         # two warm-up rounds
+            played = {}
+            for k, play in drivers.items():
+                t0 = time.perf_counter()
+                res = play(players[0], players[1], cfg, 1.0, seed=100 + i, num_games=n)
+                dt = time.perf_counter() - t0
+                played[k] = (res.wins_p1, res.wins_p2, res.rounds, res.final_states.tobytes())
+                if i >= 2:
+                    t[k].append(dt)
+            assert played["python"] == played["device"], "the two drivers played different games"
+        rows.append((f"Model vs Model, {n} games x 50 iterations", t))
+        print(rows[-1][0] + ": done", file=sys.stderr, flush=True)
+    ms = lambda x: f"{1e3 * np.median(x):.2f} ({1e3 * min(x):.2f} .. {1e3 * max(x):.2f}, {len(x)} calls)"
+    lines = ["| arena | play_tictactoe, ms: median (min .. max) | play_tictactoe_device, ms: median (min .. max) | python / device |", "|---|---|---|---|"]
+    for what, t in rows:
+        lines.append(f"| {what} | {ms(t['python'])} | {ms(t['device'])} | {np.median(t['python']) / np.median(t['device']):.2f} |")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(text + "\n")
+    print(json.dumps({what: {"python_ms": 1e3 * float(np.median(t["python"])), "device_ms": 1e3 * float(np.median(t["device"]))} for what, t in rows}))
+    for e in engines:
+        e.close()
+
+
+if __name__ == "__main__":
+    main()
