@@ -80,7 +80,11 @@ def main_tictactoe(args):
 
     def engine():
         e = Engine(0, GAME_TTT)
-        if os.environ.get("DIEE_TTT_SEARCH") == "device":                                     # opt-in: network and search on the GPU (k_ttt_search)
+        if os.environ.get("DIEE_TTT_SEARCH") == "fused":                                      # opt-in: the same, a whole search in one launch (k_ttt_search_run)
+            e.set_option("nn", "device").set_option("search", "device").set_option("search_fused", "1")
+            print("[die-e_amd] DIEE_TTT_SEARCH=fused: the tic-tac-toe searches and the network run on GPU 0, a search of independent games "
+                  "(self-play: ref_quirks off) or of at most 16 in ONE launch (k_ttt_search_run); the driver stays on the host")
+        elif os.environ.get("DIEE_TTT_SEARCH") == "device":                                   # opt-in: network and search on the GPU (k_ttt_search)
             e.set_option("nn", "device").set_option("search", "device")
             print("[die-e_amd] DIEE_TTT_SEARCH=device: the tic-tac-toe searches and the network run on GPU 0 (k_ttt_search, k_ttt_vanilla); the driver stays on the host")
         elif os.environ.get("DIEE_TTT_NN") == "device":                                       # opt-in: the network on the GPU (k_ttt_net), the search on the host

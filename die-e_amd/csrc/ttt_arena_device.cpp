@@ -49,7 +49,8 @@ void DeviceArena::run(const ArenaArgs& a, diee_arena_result* res, int8_t* winner
     for (int s = 0; s < 2; ++s) { any_model = any_model || a.agents[s] == DIEE_AGENT_MODEL; any_mcts = any_mcts || a.agents[s] == DIEE_AGENT_MCTS; }
     HIPCHK(hipSetDevice(net_.device()));
     try { reserve(n); } catch (...) { (void)hipGetLastError(); release(); throw; }
-    if (any_model) { try { search_.reserve(n, a.cfg.iterations); } catch (...) { (void)hipGetLastError(); throw; } }
+    const bool any_quirks = ((a.flags[0] | a.flags[1]) & DIEE_FLAG_REF_QUIRKS) != 0;
+    if (any_model) { try { search_.reserve(n, a.cfg.iterations, any_quirks); } catch (...) { (void)hipGetLastError(); throw; } }
     if (any_mcts) vanilla_.reserve_for(n, a.cfg);
     hipStream_t stream = net_.stream();
 

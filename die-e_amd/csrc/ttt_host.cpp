@@ -105,7 +105,7 @@ Engine::~Engine() = default;
 
 namespace {
 [[noreturn]] void unsupported_option(const std::string& key) {
-    throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has two options, `nn` and `search`; `" + key + "` belongs to a backgammon ctx");
+    throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has the options `nn`, `search`, `search_fused` and the read-only `search_last_launches` and `search_fused_lds_iters`; `" + key + "` belongs to a backgammon ctx");
 }
 }  // namespace
 
@@ -119,6 +119,13 @@ void Engine::set_option(const std::string& key, const std::string& value) {
         if (!darena_) darena_.reset(new DeviceArena(*dev_, *dsearch_, *dvanilla_));
         return;
     }
+    if (key == "search_fused") {                                             // lives in dsearch_: search = host resets it with the rest
+        if (value != "0" && value != "1") throw EngineError(DIEE_ERR_ARG, "option search_fused: `" + value + "` is neither `0` nor `1`");
+        if (value == "1" && !dsearch_) throw EngineError(DIEE_ERR_ARG, "option search_fused = 1 needs option search = device: it names a kernel of the device search");
+        if (dsearch_) dsearch_->set_fused(value == "1");
+        return;
+    }
+    if (key == "search_last_launches" || key == "search_fused_lds_iters") throw EngineError(DIEE_ERR_ARG, "option " + key + " is read-only");
     if (key != "nn") unsupported_option(key);
     if (value == "host") {
         if (dsearch_) throw EngineError(DIEE_ERR_ARG, "option nn = host while option search is `device`: set search = host first");
@@ -133,6 +140,9 @@ void Engine::set_option(const std::string& key, const std::string& value) {
 }
 std::string Engine::get_option(const std::string& key) const {
     if (key == "search") return dsearch_ ? "device" : "host";
+    if (key == "search_fused") return dsearch_ && dsearch_->fused() ? "1" : "0";
+    if (key == "search_last_launches") return std::to_string(dsearch_ ? dsearch_->last_launches() : 0u);
+    if (key == "search_fused_lds_iters") return std::to_string(kRunLdsIters);
     if (key != "nn") unsupported_option(key);
     return dev_ ? "device" : "host";
 }

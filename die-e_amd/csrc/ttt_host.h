@@ -59,6 +59,8 @@ public:
     // A failed switch to "device" (no usable GPU: DIEE_ERR_HIP) leaves the ctx on the host path.
     // option "search": "host" (default) = both searches below on the host, "device" = k_ttt_search (ttt_search_device.h) behind mcts_batch
     // and every move-step of self_play, and k_ttt_vanilla (ttt_vanilla_device.h) behind mcts_vanilla_batch.  "device" needs "nn" = "device" (else DIEE_ERR_ARG), and "nn" cannot go back to "host" before "search" has.
+    // option "search_fused": "0" (default) | "1" = an eligible device search is ONE launch of k_ttt_search_run (ttt_search_device.h); "1" needs
+    // "search" = "device" (else DIEE_ERR_ARG) and "search" = "host" resets it.  Read-only: "search_last_launches", "search_fused_lds_iters".
     // Every other key: DIEE_ERR_UNSUPPORTED.
     void set_option(const std::string& key, const std::string& value);
     std::string get_option(const std::string& key) const;

@@ -34,11 +34,28 @@ void DeviceSearch::release() {
     cap_n_ = 0; cap_nodes_ = 0; cap_out_ = 0;
 }
 
+// Which kernel a call goes to.  k_ttt_search_run serves a call whose games are independent or share one workgroup (quirks off, or n <= 16)
+// up to kRunMaxIters iterations, while every workgroup has a CU of its own: the kernel's registers hold it to one workgroup per CU in
+// either placement, k_ttt_search runs two, and measured (profiles/HISTORY.md, r18a) the one launch wins up to 4096 roots on 256 CUs and
+// loses from 8192, where its workgroups take two passes.  Its tree is in LDS while a game's bound fits (faster than HBM at every size).
+DeviceSearch::Path DeviceSearch::path(uint32_t n, uint32_t iterations, bool quirks) {
+    if (!fused_ || (quirks && n > (uint32_t)kBoardsPerGroup) || iterations > kRunMaxIters) return Path::PerIteration;
+    if (cus_ == 0) {
+        HIPCHK(hipDeviceGetAttribute(&lds_per_group_, hipDeviceAttributeMaxSharedMemoryPerBlock, net_.device()));
+        HIPCHK(hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, net_.device()));
+    }
+    if (n / kBoardsPerGroup + (n % kBoardsPerGroup != 0) > (uint32_t)cus_) return Path::PerIteration;
+    return iterations <= kRunLdsIters && lds_per_group_ >= 160 * 1024 ? Path::RunLds : Path::RunHbm;
+}
+
 // A buffer that has to grow is freed first and its capacity cleared, so a failed allocation leaves the ctx consistent (the next call
-// allocates again) and the error goes to the caller before anything has been launched.
-void DeviceSearch::reserve(uint32_t n, uint32_t iterations) {
+// allocates again) and the error goes to the caller before anything has been launched.  d_nodes_ is counted in SearchNodes (two RunNodes)
+// and reserved for the placement that needs it: k_ttt_search_run with its tree in LDS needs none.
+void DeviceSearch::reserve(uint32_t n, uint32_t iterations, bool quirks) {
     if (iterations > (0x7FFFFFFFu - 10u) / 8u) throw EngineError(DIEE_ERR_CAPACITY, "option search = device: a game's nodes are indexed with 31 bits");
-    const size_t slab = 10 + 8 * (size_t)iterations, nodes = (size_t)n * slab;
+    const Path p = path(n, iterations, quirks);
+    const size_t slab = 10 + 8 * (size_t)iterations;
+    const size_t nodes = p == Path::PerIteration ? (size_t)n * slab : p == Path::RunHbm ? ((size_t)n * run_node_bound(iterations) + 1) / 2 : 0;
     const size_t out = kCntCount * sizeof(unsigned long long) + (2 * (size_t)iterations + (size_t)n * (A + 2)) * 4;
     if (n <= cap_n_ && nodes <= cap_nodes_ && out <= cap_out_) return;
     HIPCHK(hipStreamSynchronize(net_.stream()));
@@ -80,7 +97,7 @@ void DeviceSearch::run(const diee_ttt_state* roots, uint32_t n, const diee_mcts_
         if (!ok) throw EngineError(DIEE_ERR_ARG, "option search = device: root " + std::to_string(i) + " has a cell or a player outside -1 / 0 / +1");
     }
     HIPCHK(hipSetDevice(net_.device()));
-    try { reserve(n, cfg.iterations); } catch (...) { (void)hipGetLastError(); throw; }      // (a failed allocation is not the next launch's error)
+    try { reserve(n, cfg.iterations, quirks); } catch (...) { (void)hipGetLastError(); throw; }      // (a failed allocation is not the next launch's error)
     hipStream_t stream = net_.stream();
 
     memcpy(h_roots_, roots, (size_t)n * sizeof(diee_ttt_state));
@@ -129,11 +146,22 @@ DeviceSearch::Enqueued DeviceSearch::enqueue(const diee_ttt_state* d_roots, uint
     P.c = cfg.c; P.eps = cfg.dir_eps; P.one_minus_eps = 1.0f - cfg.dir_eps;
     dirichlet_host(seed, step, cfg.dir_alpha, A, P.noise);                                       // apply_dirichlet, noise.rs:27-34: ONE sample for all rows
 
+    const Path p = path(n, cfg.iterations, quirks);
+    if (p != Path::PerIteration) P.slab = run_node_bound(cfg.iterations);
+    const size_t need = p == Path::PerIteration ? (size_t)n * P.slab : p == Path::RunHbm ? ((size_t)n * P.slab + 1) / 2 : 0;
+    if (need > cap_nodes_) throw EngineError(DIEE_ERR_CAPACITY, "option search = device: the search was not reserved for");
     HIPCHK(hipMemsetAsync(d_out_, 0, head, stream));
-    for (uint32_t k = 0; k <= cfg.iterations; ++k) {
-        P.k = k;
-        launch_ttt_search(stream, P);
-        HIPCHK(hipGetLastError());
+    if (p == Path::PerIteration) {
+        for (uint32_t k = 0; k <= cfg.iterations; ++k) {
+            P.k = k;
+            launch_ttt_search(stream, P);
+            HIPCHK(hipGetLastError());
+        }
+        last_launches_ = cfg.iterations + 1;
+    } else {
+        HIPCHK(launch_ttt_search_run(stream, P, p == Path::RunLds, p == Path::RunLds && !lds_asked_));
+        lds_asked_ = lds_asked_ || p == Path::RunLds;
+        last_launches_ = 1;
     }
     return Enqueued{P.counters, P.any_selected, P.probs, P.n_children, head, head + (size_t)n * (A + 2) * 4};
 }

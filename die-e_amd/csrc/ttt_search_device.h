@@ -1,6 +1,7 @@
 // ttt_search_device.h -- the tic-tac-toe search on the device (option "search" = "device" of a tic-tac-toe ctx whose "nn" is "device"):
 // alpha_mcts_parallel (ttt_host.cpp: search) as iterations + 1 launches of k_ttt_search (ttt_search_kernels.hip) enqueued back to back on
-// the ctx's stream, one synchronise and one copy-out at the end.  The host reads nothing in between.
+// the ctx's stream, one synchronise and one copy-out at the end.  The host reads nothing in between.  Option "search_fused" = "1" (opt-in)
+// sends an eligible call to ONE launch of k_ttt_search_run (ttt_search_run_kernels.hip) instead: same output block, same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -64,6 +65,41 @@ struct SearchParams {
 // ttt_search_kernels.hip: launch k of 0 .. iterations; ceil(n / 16) workgroups, no workgroup waits for another
 void launch_ttt_search(hipStream_t st, const SearchParams& P);
 
+// ---- k_ttt_search_run: the whole search of a workgroup's 16 games in one launch ------------------------------------------------------------------
+// A node of its tree, 16 bytes: a child's action and state follow from the parent's state (child j is the j-th empty cell in ascending
+// order) and the path of a descent is written down, so neither is stored.
+struct RunNode {
+    float visits, value, prior;
+    uint32_t link;             // first_child | n_children << 16 | drained << 20
+};
+static_assert(sizeof(RunNode) == 16, "one 16-byte load per child");
+constexpr uint32_t kRunDrained = 1u << 20;
+// The most nodes a game's tree can hold after `iterations` iterations.  Level d of a tic-tac-toe tree has at most 9 * 8 * .. * (10 - d)
+// nodes, each with at most 9 - d children; the root is expanded before the first iteration and an iteration expands at most one node.  The
+// sum is largest when the expansions go to the shallowest levels first: 9 nodes of 8 children, 72 of 7, 504 of 6, ...  (369 at 50.)
+constexpr uint32_t run_node_bound(uint32_t iterations) {
+    uint32_t nodes = 10, level = 9;
+    for (uint32_t d = 1; d < 9 && iterations != 0; ++d) {
+        const uint32_t e = iterations < level ? iterations : level;
+        nodes += e * (9 - d); iterations -= e; level *= 9 - d;
+    }
+    return nodes;
+}
+static_assert(run_node_bound(0) == 10 && run_node_bound(9) == 82 && run_node_bound(50) == 369 && run_node_bound(0xFFFFFFFFu) == 986410, "");
+// The tree stays in LDS while the 16 games' bounds fit into what the network's 62400 bytes (NetLds) and the kernel's own 1280 leave of a
+// CU's 160 KB; above that it lies in the HBM slab.  kRunLdsIters is the largest `iterations` of the LDS placement.
+constexpr uint32_t kRunLdsBytes = 160 * 1024 - 62400 - 1280;
+constexpr uint32_t run_lds_iters() {
+    uint32_t it = 0;
+    while (run_node_bound(it + 1) * 16 * sizeof(RunNode) <= kRunLdsBytes) ++it;
+    return it;
+}
+constexpr uint32_t kRunLdsIters = run_lds_iters();
+constexpr uint32_t kRunMaxIters = 4096;            // k_ttt_vanilla's bound: a launch stays far below a second
+// ttt_search_run_kernels.hip: ceil(n / 16) workgroups; P.k is unused, P.slab = run_node_bound(iterations), P.nodes (RunNode [n][slab]) only
+// if !lds_tree.  `first`: no launch with the tree in LDS has been made on this device yet (the dynamic LDS has to be asked for once).
+hipError_t launch_ttt_search_run(hipStream_t st, const SearchParams& P, bool lds_tree, bool first);
+
 // The buffers of the device search, owned by the ctx, grown by doubling; results of one call in page-locked memory.
 class DeviceSearch {
 public:
@@ -85,10 +121,21 @@ public:
     // stream over `net` (this ctx's network, or another ctx's on the same device: read-only), nothing copied and nothing waited for.
     // The caller has reserved (n or more games, cfg.iterations) and set the device.
     Enqueued enqueue(const diee_ttt_state* d_roots, uint32_t n, const NetParams& net, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step, bool quirks);
-    void reserve(uint32_t n, uint32_t iterations);
+    // `quirks`: whether any search to come runs under DIEE_FLAG_REF_QUIRKS (it decides which kernel a call goes to, and so what it needs)
+    void reserve(uint32_t n, uint32_t iterations, bool quirks);
+    // option "search_fused" and what the read-only options report
+    void set_fused(bool on) { fused_ = on; }
+    bool fused() const { return fused_; }
+    uint32_t last_launches() const { return last_launches_; }
 
 private:
+    enum class Path { PerIteration, RunLds, RunHbm };
+    Path path(uint32_t n, uint32_t iterations, bool quirks);
     void release();
+    bool fused_ = false;
+    uint32_t last_launches_ = 0;               // search-kernel launches of the last enqueue()
+    int cus_ = 0, lds_per_group_ = 0;          // of the device, asked once
+    bool lds_asked_ = false;                   // k_ttt_search_run's dynamic LDS has been asked for
     DeviceNet& net_;
     void *d_roots_ = nullptr, *d_nodes_ = nullptr, *d_games_ = nullptr, *d_out_ = nullptr, *h_roots_ = nullptr, *h_out_ = nullptr;
     // d_out_ / h_out_: counters [kCntCount] u64 | any_selected [iterations] | never_selected [iterations] | probs [n][9] | n_children [n] | root_visits [n], copied out as one

@@ -66,7 +66,7 @@ typedef struct {
  * self-play driver in C++ on the HOST (die-e_amd/csrc/ttt_host.cpp) and needs no GPU; its states are diee_ttt_state
  * records (cast the pointer where a prototype says diee_bg_state), policies / ps rows have 9 entries, planes 27.
  * Served for such a ctx: diee_load_weights, diee_nn_forward, diee_mcts_batch, diee_ttt_mcts_vanilla_batch, diee_ttt_arena, diee_self_play (+ lifetime /
- * error calls) and the two options "nn" and "search" (below); everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no
+ * error calls) and the options "nn", "search" and "search_fused" (below); everything else answers DIEE_ERR_UNSUPPORTED.  The backgammon ctx has no
  * host path. */
 typedef struct {
     int8_t  board[9];          /* 0 | 1 | 2 / 3 | 4 | 5 / 6 | 7 | 8; -1 / 0 / +1            */
@@ -221,6 +221,17 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *                                 The option names where BOTH searches of the ctx run: diee_ttt_mcts_vanilla_batch (Agent::Mcts, no network) runs
  *                                 as launches of k_ttt_vanilla, up to 4096 whole iterations per game and launch, with the same bits as on "host".
  *                                 That search needs no weights: a weightless ctx may set "nn" = "device", then "search" = "device".
+ *   search_fused          "0" | "1"   TIC-TAC-TOE ctx only.  "1": a search of k_ttt_search whose games are independent or share one workgroup --
+ *                                 without DIEE_FLAG_REF_QUIRKS, or with at most 16 roots --, of at most 4096 iterations and of at most 16 roots per
+ *                                 CU of the device (4096 on an MI355X: beyond, one launch was measured slower) is ONE launch of
+ *                                 k_ttt_search_run: a workgroup keeps its 16 games in registers and LDS for the whole search (the tree in LDS up to
+ *                                 search_fused_lds_iters iterations, in HBM above).  Every other call takes the iterations + 1 launches.  Same results
+ *                                 and statistics, bit for bit.  It serves diee_mcts_batch, diee_self_play and the Model searches of diee_ttt_arena on
+ *                                 the hosting ctx.  "1" is accepted only while "search" is "device" (else DIEE_ERR_ARG), any other value is
+ *                                 DIEE_ERR_ARG, and "search" = "host" resets it.  Default "0".
+ *   search_last_launches  READ-ONLY, tic-tac-toe ctx: the search-kernel launches the ctx's last device search enqueued, iterations + 1 or 1
+ *                                 (0 before the first, and on "search" = "host")
+ *   search_fused_lds_iters  READ-ONLY, tic-tac-toe ctx: the largest `iterations` whose tree k_ttt_search_run keeps in LDS (53)
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
  *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
  *                                 diee_self_play_refill of this ctx allocated: min(width, games of the call), whatever the call's length

@@ -8,7 +8,9 @@ who runs a round between them -- Python (a copy-out and a synchronise per search
 k_ttt_arena_split / k_ttt_arena_move (three words per round).  Temperature 1.0, where both drivers sample from the same rows, so every
 timed pair is also checked to have played the same games.  Every call is synchronous on return, so a host clock around it is a call time.
 Each row is warmed up on both drivers, the two alternate rep by rep; the table gives the median and the spread, and a difference counts only
-if it exceeds that spread.  Prints a markdown table and, last, one JSON line."""
+if it exceeds that spread.  A second table is diee_ttt_arena alone with flags 0 (the quirks off), option search_fused = 0 against 1 on the
+hosting ctx: one launch of k_ttt_search per iteration against one of k_ttt_search_run per search, same games checked.  Prints the markdown
+tables and, last, one JSON line."""
 import argparse
 import json
 import os
@@ -50,16 +52,37 @@ def main():
             assert played["python"] == played["device"], "the two drivers played different games"
         rows.append((f"Model vs Model, {n} games x 50 iterations", t))
         print(rows[-1][0] + ": done", file=sys.stderr, flush=True)
+    fused_rows = []
+    for n in (16, 400):
+        t = {"0": [], "1": []}
+        for i in range(a.reps + 2):
+            played = {}
+            for k in t:
+                engines[0].set_option("search_fused", k)
+                t0 = time.perf_counter()
+                r = diee_amd.ttt_arena(engines[0], diee_amd.AGENT_MODEL, engines[1], diee_amd.AGENT_MODEL, n, cfg, 1.0, seed=100 + i, flags=[0, 0])
+                dt = time.perf_counter() - t0
+                played[k] = (r["wins_p1"], r["wins_p2"], r["rounds"], r["final_states"].tobytes())
+                if i >= 2:
+                    t[k].append(dt)
+            assert played["0"] == played["1"], "the two kernels played different games"
+        fused_rows.append((f"diee_ttt_arena flags 0, {n} games x 50 iterations", t))
+        print(fused_rows[-1][0] + ": done", file=sys.stderr, flush=True)
+    engines[0].set_option("search_fused", "0")
     ms = lambda x: f"{1e3 * np.median(x):.2f} ({1e3 * min(x):.2f} .. {1e3 * max(x):.2f}, {len(x)} calls)"
     lines = ["| arena | play_tictactoe, ms: median (min .. max) | play_tictactoe_device, ms: median (min .. max) | python / device |", "|---|---|---|---|"]
     for what, t in rows:
         lines.append(f"| {what} | {ms(t['python'])} | {ms(t['device'])} | {np.median(t['python']) / np.median(t['device']):.2f} |")
+    lines += ["", "| arena | search_fused = 0, ms: median (min .. max) | search_fused = 1, ms: median (min .. max) | 0 / 1 |", "|---|---|---|---|"]
+    for what, t in fused_rows:
+        lines.append(f"| {what} | {ms(t['0'])} | {ms(t['1'])} | {np.median(t['0']) / np.median(t['1']):.2f} |")
     text = "\n".join(lines)
     print(text)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         open(a.out, "w").write(text + "\n")
-    print(json.dumps({what: {"python_ms": 1e3 * float(np.median(t["python"])), "device_ms": 1e3 * float(np.median(t["device"]))} for what, t in rows}))
+    print(json.dumps({what: {"python_ms": 1e3 * float(np.median(t["python"])), "device_ms": 1e3 * float(np.median(t["device"]))} for what, t in rows}
+                     | {what: {"per_iteration_ms": 1e3 * float(np.median(t["0"])), "fused_ms": 1e3 * float(np.median(t["1"]))} for what, t in fused_rows}))
     for e in engines:
         e.close()
 
