@@ -231,10 +231,12 @@ class AlphaZero:
         n = self.config.num_self_play_batches
         self.calls += 1
         # opt-in (DIEE_TTT_SEARCH=fused; as DIEE_REFILL_WIDTH below): Q14 is what couples the games of a search, so the one-launch search
-        # (k_ttt_search_run) serves more than 16 games only without the quirks
-        quirks = not (self.game is TICTACTOE and self.engine.get_option("search_fused") == "1")
+        # (k_ttt_search_run) serves more than 16 games only without the quirks; DIEE_TTT_SEARCH=game: the whole call is one launch (k_ttt_selfplay_run)
+        fused = self.engine.get_option("search_fused") if self.game is TICTACTOE else "0"
+        quirks = fused not in ("1", "2")
         if not quirks and self.calls == 1:
-            self.log("[self-play] search_fused = 1: every search is one launch (k_ttt_search_run), ref_quirks off")
+            self.log(f"[self-play] search_fused = {fused}: every " + ("self-play call is one launch (k_ttt_selfplay_run)" if fused == "2" else
+                                                                      "search is one launch (k_ttt_search_run)") + ", ref_quirks off")
         out = self.engine.self_play_parallel(n, self.mcts_config, self.config.temperature,
                                              seed=self.seed + 0x9E3779B1 * self.calls, ref_quirks=quirks,
                                              first_game_id=self.rank * n)

@@ -80,7 +80,11 @@ def main_tictactoe(args):
 
     def engine():
         e = Engine(0, GAME_TTT)
-        if os.environ.get("DIEE_TTT_SEARCH") == "fused":                                      # opt-in: the same, a whole search in one launch (k_ttt_search_run)
+        if os.environ.get("DIEE_TTT_SEARCH") == "game":                                       # opt-in: as fused, and a self-play call in one launch (k_ttt_selfplay_run)
+            e.set_option("nn", "device").set_option("search", "device").set_option("search_fused", "2")
+            print("[die-e_amd] DIEE_TTT_SEARCH=game: as DIEE_TTT_SEARCH=fused, and a self-play call (ref_quirks off) is ONE search-and-play launch "
+                  "(k_ttt_selfplay_run) plus the delivery of its records; every other driver stays on the host")
+        elif os.environ.get("DIEE_TTT_SEARCH") == "fused":                                    # opt-in: the same, a whole search in one launch (k_ttt_search_run)
             e.set_option("nn", "device").set_option("search", "device").set_option("search_fused", "1")
             print("[die-e_amd] DIEE_TTT_SEARCH=fused: the tic-tac-toe searches and the network run on GPU 0, a search of independent games "
                   "(self-play: ref_quirks off) or of at most 16 in ONE launch (k_ttt_search_run); the driver stays on the host")

@@ -129,20 +129,9 @@ __global__ __launch_bounds__(256) DIEE_TTT_NO_PK_F32 void k_ttt_arena_move(Arena
         if (AGENT == DIEE_AGENT_MODEL) {                                               // :279-299
             const float x = j < 9 ? M.probs[slot * 9 + (size_t)j] : 0.f;
             const float w = det_powf(x > 0.f ? x : 0.f, M.inv_t);                      // (NaN, the row of a childless root: 0)
-            double total = 0.0;
-#pragma unroll
-            for (int c = 0; c < 9; ++c) total += (double)row_getf(w, row0 + c);
-            const double thr = u * total;
-            double cum = 0.0;
-            int pick = -1, last_nz = 0;
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                const float wc = row_getf(w, row0 + c);
-                if (wc != 0.f) last_nz = c;
-                cum += (double)wc;
-                if (pick < 0 && cum > thr) pick = c;
-            }
-            if (M.n_children[slot] != 0u && total > 0.0) move = pick < 0 ? last_nz : pick;      // :286-293: else EMPTY_MOVE
+            double total;
+            const int pick = weighted_pick(w, u, row0, total);
+            if (M.n_children[slot] != 0u && total > 0.0) move = pick;                  // :286-293: else EMPTY_MOVE
         } else {                                                                       // :308-317
             const uint32_t mask = row_ballot(j < 9 && cell_of(st, j < 9 ? j : 0) == 0, row0);
             const int count = __builtin_popcount(mask);

@@ -18,6 +18,7 @@
 #include "ttt_arena_device.h"
 #include "ttt_device.h"
 #include "ttt_search_device.h"
+#include "ttt_selfplay_device.h"
 #include "ttt_vanilla_device.h"
 #include "vanilla_host.h"
 
@@ -105,27 +106,28 @@ Engine::~Engine() = default;
 
 namespace {
 [[noreturn]] void unsupported_option(const std::string& key) {
-    throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has the options `nn`, `search`, `search_fused` and the read-only `search_last_launches` and `search_fused_lds_iters`; `" + key + "` belongs to a backgammon ctx");
+    throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has the options `nn`, `search`, `search_fused` and the read-only `search_last_launches`, `self_play_last_launches` and `search_fused_lds_iters`; `" + key + "` belongs to a backgammon ctx");
 }
 }  // namespace
 
 void Engine::set_option(const std::string& key, const std::string& value) {
     if (key == "search") {
-        if (value == "host") { darena_.reset(); dsearch_.reset(); dvanilla_.reset(); return; }
+        if (value == "host") { dselfplay_.reset(); darena_.reset(); dsearch_.reset(); dvanilla_.reset(); return; }
         if (value != "device") throw EngineError(DIEE_ERR_ARG, "option search: `" + value + "` is neither `host` nor `device`");
         if (!dev_) throw EngineError(DIEE_ERR_ARG, "option search = device needs option nn = device: the device search evaluates the device network");
         if (!dvanilla_) dvanilla_.reset(new DeviceVanilla(*dev_));
         if (!dsearch_) dsearch_.reset(new DeviceSearch(*dev_));              // buffers come with the first search
         if (!darena_) darena_.reset(new DeviceArena(*dev_, *dsearch_, *dvanilla_));
+        if (!dselfplay_) dselfplay_.reset(new DeviceSelfPlay(*dev_, *dsearch_));
         return;
     }
     if (key == "search_fused") {                                             // lives in dsearch_: search = host resets it with the rest
-        if (value != "0" && value != "1") throw EngineError(DIEE_ERR_ARG, "option search_fused: `" + value + "` is neither `0` nor `1`");
-        if (value == "1" && !dsearch_) throw EngineError(DIEE_ERR_ARG, "option search_fused = 1 needs option search = device: it names a kernel of the device search");
-        if (dsearch_) dsearch_->set_fused(value == "1");
+        if (value != "0" && value != "1" && value != "2") throw EngineError(DIEE_ERR_ARG, "option search_fused: `" + value + "` is none of `0`, `1`, `2`");
+        if (value != "0" && !dsearch_) throw EngineError(DIEE_ERR_ARG, "option search_fused = " + value + " needs option search = device: it names a kernel of the device search");
+        if (dsearch_) dsearch_->set_fused((uint32_t)(value[0] - '0'));
         return;
     }
-    if (key == "search_last_launches" || key == "search_fused_lds_iters") throw EngineError(DIEE_ERR_ARG, "option " + key + " is read-only");
+    if (key == "search_last_launches" || key == "self_play_last_launches" || key == "search_fused_lds_iters") throw EngineError(DIEE_ERR_ARG, "option " + key + " is read-only");
     if (key != "nn") unsupported_option(key);
     if (value == "host") {
         if (dsearch_) throw EngineError(DIEE_ERR_ARG, "option nn = host while option search is `device`: set search = host first");
@@ -140,8 +142,9 @@ void Engine::set_option(const std::string& key, const std::string& value) {
 }
 std::string Engine::get_option(const std::string& key) const {
     if (key == "search") return dsearch_ ? "device" : "host";
-    if (key == "search_fused") return dsearch_ && dsearch_->fused() ? "1" : "0";
+    if (key == "search_fused") return std::to_string(dsearch_ ? dsearch_->fused_level() : 0u);
     if (key == "search_last_launches") return std::to_string(dsearch_ ? dsearch_->last_launches() : 0u);
+    if (key == "self_play_last_launches") return std::to_string(dsearch_ ? dsearch_->self_play_launches() : 0u);
     if (key == "search_fused_lds_iters") return std::to_string(kRunLdsIters);
     if (key != "nn") unsupported_option(key);
     return dev_ ? "device" : "host";
@@ -168,7 +171,7 @@ void Engine::load_weights(const float* blob, size_t n) {
     w_.assign(blob, blob + n);
     // a failed upload must not leave "device" answering with the previous network: the ctx falls back to "host" (which holds the new
     // weights, and the host search with it) and the caller gets the HIP error, as in set_option
-    if (dev_) { try { upload(); } catch (...) { darena_.reset(); dsearch_.reset(); dvanilla_.reset(); dev_.reset(); throw; } }
+    if (dev_) { try { upload(); } catch (...) { dselfplay_.reset(); darena_.reset(); dsearch_.reset(); dvanilla_.reset(); dev_.reset(); throw; } }
 }
 
 // ---- the network, fp32 ------------------------------------------------------------------------------------------------
@@ -390,6 +393,13 @@ void Engine::self_play(uint32_t n_games, uint32_t first_game_id, const diee_mcts
     const bool quirks = (flags & DIEE_FLAG_REF_QUIRKS) != 0;
     const float inv_t = (float)(1.0 / (double)temperature);                                // :165 pow_(1.0 / temperature)
     const auto t0 = std::chrono::steady_clock::now();
+    // option search_fused = 2: the whole call is one search-and-play launch and the delivery (ttt_selfplay_device.h); the quirks couple the
+    // games of a move-step through the live list, so a call under them takes the loop below
+    if (dselfplay_ && dsearch_->fused_level() == 2 && !quirks && dselfplay_->serves(n_games, cfg.iterations)) {
+        dselfplay_->run(n_games, first_game_id, cfg, temperature, seed, max_steps, out, stats);
+        if (stats) stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return;
+    }
     struct Frag { int8_t player; float ps[A]; float st[PLANES]; };
     std::vector<diee_ttt_state> states(n_games);
     std::vector<uint32_t> rounds(n_games, 0);
@@ -404,7 +414,7 @@ void Engine::self_play(uint32_t n_games, uint32_t first_game_id, const diee_mcts
         }
     };
     for (uint32_t g = 0; g < n_games; ++g) { memset(&states[g], 0, sizeof states[g]); states[g].player = -1; }   // TicTacToe::new, mod.rs:28-30
-    uint32_t n_live = n_games, steps = 0;
+    uint32_t n_live = n_games, steps = 0, launches = 0;
     std::vector<diee_ttt_state> roots; std::vector<uint32_t> ids;
     std::vector<float> row(A);
     RootResult R;
@@ -412,6 +422,7 @@ void Engine::self_play(uint32_t n_games, uint32_t first_game_id, const diee_mcts
         roots.clear(); ids.clear();
         for (uint32_t g = 0; g < n_games; ++g) if (live[g]) { roots.push_back(states[g]); ids.push_back(g); }
         search(roots.data(), (uint32_t)roots.size(), cfg, seed, steps, quirks, stats, R);   // :137 a fresh NodeStore every move-step, :146
+        if (dsearch_) launches += dsearch_->last_launches();
         for (size_t pi = 0; pi < ids.size(); ++pi) {                                       // :168-224
             const uint32_t g = ids[pi];
             bool removed = false, flushed = false;
@@ -445,6 +456,7 @@ void Engine::self_play(uint32_t n_games, uint32_t first_game_id, const diee_mcts
         }
         ++steps;
     }
+    if (dsearch_) dsearch_->report_launches(dsearch_->last_launches(), launches);
     const size_t nf = o_outcome.size();
     if (stats) {
         stats->move_steps = steps; stats->fragments = nf; stats->nn_rows = stats->nn_evals;

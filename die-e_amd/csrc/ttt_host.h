@@ -43,6 +43,7 @@ class DeviceNet;                                                          // ttt
 class DeviceSearch;                                                       // ttt_search_device.h
 class DeviceVanilla;                                                      // ttt_vanilla_device.h
 class DeviceArena;                                                        // ttt_arena_device.h
+class DeviceSelfPlay;                                                     // ttt_selfplay_device.h
 
 // what a search leaves for its callers: get_prob_tensor_parallel's rows (utils.rs:42-58) and the roots' counts
 struct RootResult {
@@ -60,7 +61,9 @@ public:
     // option "search": "host" (default) = both searches below on the host, "device" = k_ttt_search (ttt_search_device.h) behind mcts_batch
     // and every move-step of self_play, and k_ttt_vanilla (ttt_vanilla_device.h) behind mcts_vanilla_batch.  "device" needs "nn" = "device" (else DIEE_ERR_ARG), and "nn" cannot go back to "host" before "search" has.
     // option "search_fused": "0" (default) | "1" = an eligible device search is ONE launch of k_ttt_search_run (ttt_search_device.h); "1" needs
-    // "search" = "device" (else DIEE_ERR_ARG) and "search" = "host" resets it.  Read-only: "search_last_launches", "search_fused_lds_iters".
+    // "search" = "device" (else DIEE_ERR_ARG) and "search" = "host" resets it.  "2" = "1", and a self_play call without the quirks whose
+    // workgroups have a CU each is ONE launch of k_ttt_selfplay_run plus the delivery (ttt_selfplay_device.h).  Read-only: "search_last_launches",
+    // "self_play_last_launches" (the search launches of the last self_play), "search_fused_lds_iters".
     // Every other key: DIEE_ERR_UNSUPPORTED.
     void set_option(const std::string& key, const std::string& value);
     std::string get_option(const std::string& key) const;
@@ -96,6 +99,7 @@ private:
     std::unique_ptr<DeviceSearch> dsearch_;                                 // non-null = "search" is "device" (dev_ is non-null then; declared after it: destroyed first)
     std::unique_ptr<DeviceVanilla> dvanilla_;                               // set and cleared with dsearch_
     std::unique_ptr<DeviceArena> darena_;                                   // set and cleared with dsearch_; it drives the two above (destroyed before them)
+    std::unique_ptr<DeviceSelfPlay> dselfplay_;                             // set and cleared with dsearch_, whose device limits and launch counts it uses (destroyed before it)
     Conv init_, c1_[BLOCKS], c2_[BLOCKS], pconv_, vconv_;
     std::vector<float> pfc_w_, pfc_b_, vfc_w_, vfc_b_;
     std::vector<float> w_;                                                  // the blob as loaded (non-empty = loaded)

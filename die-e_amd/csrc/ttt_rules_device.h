@@ -41,5 +41,25 @@ DIEE_TTT_FN uint32_t row_get(uint32_t v, int src_lane) { return (uint32_t)__buil
 DIEE_TTT_FN float row_getf(float v, int src_lane) { return as_f32(row_get(__builtin_bit_cast(uint32_t, v), src_lane)); }
 DIEE_TTT_FN uint32_t row_ballot(bool p, int row0) { return (uint32_t)(__builtin_amdgcn_ballot_w64(p) >> row0) & 0xFFFFu; }
 
+// weighted_select of ttt_host.cpp (alphazero.rs:129-137, rand's WeightedIndex over f64) on a row: lane j < 9 brings the weight of cell j
+// (the other lanes 0), every lane replays the sequential f64 sum of the nine in cell order, then the running sum against u * total: the
+// first cell that exceeds it, of rounding's leftovers the last non-zero one.  All lanes of the wave come here.
+DIEE_TTT_FN int weighted_pick(float w, double u, int row0, double& total) {
+    total = 0.0;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) total += (double)row_getf(w, row0 + c);
+    const double thr = u * total;
+    double cum = 0.0;
+    int pick = -1, last_nz = 0;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+        const float wc = row_getf(w, row0 + c);
+        if (wc != 0.f) last_nz = c;
+        cum += (double)wc;
+        if (pick < 0 && cum > thr) pick = c;
+    }
+    return pick < 0 ? last_nz : pick;
+}
+
 }  // namespace ttt
 }  // namespace diee

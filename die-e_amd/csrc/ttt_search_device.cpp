@@ -40,12 +40,18 @@ void DeviceSearch::release() {
 // loses from 8192, where its workgroups take two passes.  Its tree is in LDS while a game's bound fits (faster than HBM at every size).
 DeviceSearch::Path DeviceSearch::path(uint32_t n, uint32_t iterations, bool quirks) {
     if (!fused_ || (quirks && n > (uint32_t)kBoardsPerGroup) || iterations > kRunMaxIters) return Path::PerIteration;
+    int cus, lds;
+    limits(cus, lds);
+    if (n / kBoardsPerGroup + (n % kBoardsPerGroup != 0) > (uint32_t)cus) return Path::PerIteration;
+    return iterations <= kRunLdsIters && lds >= 160 * 1024 ? Path::RunLds : Path::RunHbm;
+}
+
+void DeviceSearch::limits(int& cus, int& lds_per_group) {
     if (cus_ == 0) {
         HIPCHK(hipDeviceGetAttribute(&lds_per_group_, hipDeviceAttributeMaxSharedMemoryPerBlock, net_.device()));
         HIPCHK(hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, net_.device()));
     }
-    if (n / kBoardsPerGroup + (n % kBoardsPerGroup != 0) > (uint32_t)cus_) return Path::PerIteration;
-    return iterations <= kRunLdsIters && lds_per_group_ >= 160 * 1024 ? Path::RunLds : Path::RunHbm;
+    cus = cus_; lds_per_group = lds_per_group_;
 }
 
 // A buffer that has to grow is freed first and its capacity cleared, so a failed allocation leaves the ctx consistent (the next call

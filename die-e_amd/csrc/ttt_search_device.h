@@ -123,17 +123,24 @@ public:
     Enqueued enqueue(const diee_ttt_state* d_roots, uint32_t n, const NetParams& net, const diee_mcts_cfg& cfg, uint64_t seed, uint32_t step, bool quirks);
     // `quirks`: whether any search to come runs under DIEE_FLAG_REF_QUIRKS (it decides which kernel a call goes to, and so what it needs)
     void reserve(uint32_t n, uint32_t iterations, bool quirks);
-    // option "search_fused" and what the read-only options report
-    void set_fused(bool on) { fused_ = on; }
-    bool fused() const { return fused_; }
+    // option "search_fused" (0, 1, or 2: as 1, and an eligible self-play call is one launch, ttt_selfplay_device.h) and what the read-only options report
+    void set_fused(uint32_t level) { fused_ = level != 0; fused_level_ = level; }
+    uint32_t fused_level() const { return fused_level_; }
     uint32_t last_launches() const { return last_launches_; }
+    uint32_t self_play_launches() const { return self_play_launches_; }
+    // what a self-play call has launched: its last search | all its searches
+    void report_launches(uint32_t last, uint32_t self_play) { last_launches_ = last; self_play_launches_ = self_play; }
+    // the device's CUs and the LDS a workgroup can have, asked once
+    void limits(int& cus, int& lds_per_group);
 
 private:
     enum class Path { PerIteration, RunLds, RunHbm };
     Path path(uint32_t n, uint32_t iterations, bool quirks);
     void release();
     bool fused_ = false;
+    uint32_t fused_level_ = 0;
     uint32_t last_launches_ = 0;               // search-kernel launches of the last enqueue()
+    uint32_t self_play_launches_ = 0;          // search-kernel launches of the last self-play call
     int cus_ = 0, lds_per_group_ = 0;          // of the device, asked once
     bool lds_asked_ = false;                   // k_ttt_search_run's dynamic LDS has been asked for
     DeviceNet& net_;

@@ -227,10 +227,17 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *                                 k_ttt_search_run: a workgroup keeps its 16 games in registers and LDS for the whole search (the tree in LDS up to
  *                                 search_fused_lds_iters iterations, in HBM above).  Every other call takes the iterations + 1 launches.  Same results
  *                                 and statistics, bit for bit.  It serves diee_mcts_batch, diee_self_play and the Model searches of diee_ttt_arena on
- *                                 the hosting ctx.  "1" is accepted only while "search" is "device" (else DIEE_ERR_ARG), any other value is
- *                                 DIEE_ERR_ARG, and "search" = "host" resets it.  Default "0".
+ *                                 the hosting ctx.  "2": as "1" for every search, and a diee_self_play call without DIEE_FLAG_REF_QUIRKS, of at
+ *                                 most 4096 iterations and of at most 16 games per CU, is ONE launch of k_ttt_selfplay_run -- a workgroup carries
+ *                                 its 16 games from the empty board to their last move: search, sampling, the records, the rules -- and two
+ *                                 small delivery kernels; same records and statistics, bit for bit.  Every other diee_self_play call keeps the
+ *                                 host loop over one search per move-step.  "1" and "2" are accepted only while "search" is "device" (else
+ *                                 DIEE_ERR_ARG), any other value is DIEE_ERR_ARG, and "search" = "host" resets it.  Default "0".
  *   search_last_launches  READ-ONLY, tic-tac-toe ctx: the search-kernel launches the ctx's last device search enqueued, iterations + 1 or 1
- *                                 (0 before the first, and on "search" = "host")
+ *                                 (0 before the first, and on "search" = "host"; 1 after a one-launch diee_self_play)
+ *   self_play_last_launches  READ-ONLY, tic-tac-toe ctx: the search-kernel launches of the ctx's last diee_self_play: the sum of
+ *                                 search_last_launches over its move-steps, 1 for the one-launch call ("search_fused" = "2"), 0 before the
+ *                                 first and on "search" = "host"
  *   search_fused_lds_iters  READ-ONLY, tic-tac-toe ctx: the largest `iterations` whose tree k_ttt_search_run keeps in LDS (53)
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
  *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
