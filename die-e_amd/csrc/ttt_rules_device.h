@@ -1,7 +1,7 @@
-// ttt_rules_device.h -- the tic-tac-toe rules on a packed state word and the row-of-16-lanes helpers, shared by k_ttt_search
-// (ttt_search_kernels.hip) and the arena kernels (ttt_arena_kernels.hip).  The word is SearchNode::state's: 2 bits per cell (0 empty,
-// 1 = +1, 3 = -1) in bits 0 .. 17, bit 18 = the player to move is +1.  Everything is DIEE_TTT_NO_PK_F32 and nothing but builtins, so it
-// inlines into the kernels of the family (ttt_net_device.h says why).
+// ttt_rules_device.h -- the tic-tac-toe rules on a packed state word and the row-of-16-lanes helpers, shared by the device search
+// (ttt_search_iter_device.h) and the arena kernels (ttt_arena_kernels.hip).  The word: 2 bits per cell (0 empty, 1 = +1, 3 = -1) in
+// bits 0 .. 17, bit 18 = the player to move is +1.  Everything is DIEE_TTT_NO_PK_F32 and nothing but builtins, so it inlines into the
+// kernels of the family (ttt_net_device.h says why).
 #pragma once
 #include <hip/hip_runtime.h>
 

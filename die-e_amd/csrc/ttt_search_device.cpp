@@ -55,13 +55,12 @@ void DeviceSearch::limits(int& cus, int& lds_per_group) {
 }
 
 // A buffer that has to grow is freed first and its capacity cleared, so a failed allocation leaves the ctx consistent (the next call
-// allocates again) and the error goes to the caller before anything has been launched.  d_nodes_ is counted in SearchNodes (two RunNodes)
-// and reserved for the placement that needs it: k_ttt_search_run with its tree in LDS needs none.
+// allocates again) and the error goes to the caller before anything has been launched.  d_nodes_ is reserved for the placement that needs
+// it: k_ttt_search_run with its tree in LDS needs none.
 void DeviceSearch::reserve(uint32_t n, uint32_t iterations, bool quirks) {
     if (iterations > (0x7FFFFFFFu - 10u) / 8u) throw EngineError(DIEE_ERR_CAPACITY, "option search = device: a game's nodes are indexed with 31 bits");
     const Path p = path(n, iterations, quirks);
-    const size_t slab = 10 + 8 * (size_t)iterations;
-    const size_t nodes = p == Path::PerIteration ? (size_t)n * slab : p == Path::RunHbm ? ((size_t)n * run_node_bound(iterations) + 1) / 2 : 0;
+    const size_t nodes = p == Path::RunLds ? 0 : (size_t)n * run_node_bound(iterations);
     const size_t out = kCntCount * sizeof(unsigned long long) + (2 * (size_t)iterations + (size_t)n * (A + 2)) * 4;
     if (n <= cap_n_ && nodes <= cap_nodes_ && out <= cap_out_) return;
     HIPCHK(hipStreamSynchronize(net_.stream()));
@@ -78,7 +77,7 @@ void DeviceSearch::reserve(uint32_t n, uint32_t iterations, bool quirks) {
         const size_t cap = grown(cap_nodes_, nodes, 1024 * 64);
         drop(d_nodes_, false);
         cap_nodes_ = 0;
-        HIPCHK(hipMalloc(&d_nodes_, cap * sizeof(SearchNode)));
+        HIPCHK(hipMalloc(&d_nodes_, cap * sizeof(RunNode)));
         cap_nodes_ = cap;
     }
     if (out > cap_out_) {
@@ -138,7 +137,7 @@ DeviceSearch::Enqueued DeviceSearch::enqueue(const diee_ttt_state* d_roots, uint
     SearchParams P{};
     P.net = net;
     P.roots = d_roots;
-    P.nodes = (SearchNode*)d_nodes_;
+    P.nodes = (RunNode*)d_nodes_;
     P.games = (SearchGame*)d_games_;
     unsigned char* o = (unsigned char*)d_out_;
     const size_t head = kCntCount * sizeof(unsigned long long) + 2 * (size_t)cfg.iterations * 4;     // counters and per-iteration words: cleared in-stream
@@ -148,14 +147,12 @@ DeviceSearch::Enqueued DeviceSearch::enqueue(const diee_ttt_state* d_roots, uint
     P.probs = (float*)(o + head);
     P.n_children = (uint32_t*)(P.probs + (size_t)n * A);
     P.root_visits = (float*)(P.n_children + n);
-    P.n = n; P.iterations = cfg.iterations; P.slab = 10 + 8 * cfg.iterations; P.quirks = quirks ? 1u : 0u;
+    P.n = n; P.iterations = cfg.iterations; P.slab = run_node_bound(cfg.iterations); P.quirks = quirks ? 1u : 0u;
     P.c = cfg.c; P.eps = cfg.dir_eps; P.one_minus_eps = 1.0f - cfg.dir_eps;
     dirichlet_host(seed, step, cfg.dir_alpha, A, P.noise);                                       // apply_dirichlet, noise.rs:27-34: ONE sample for all rows
 
     const Path p = path(n, cfg.iterations, quirks);
-    if (p != Path::PerIteration) P.slab = run_node_bound(cfg.iterations);
-    const size_t need = p == Path::PerIteration ? (size_t)n * P.slab : p == Path::RunHbm ? ((size_t)n * P.slab + 1) / 2 : 0;
-    if (need > cap_nodes_) throw EngineError(DIEE_ERR_CAPACITY, "option search = device: the search was not reserved for");
+    if ((p == Path::RunLds ? 0 : (size_t)n * P.slab) > cap_nodes_) throw EngineError(DIEE_ERR_CAPACITY, "option search = device: the search was not reserved for");
     HIPCHK(hipMemsetAsync(d_out_, 0, head, stream));
     if (p == Path::PerIteration) {
         for (uint32_t k = 0; k <= cfg.iterations; ++k) {

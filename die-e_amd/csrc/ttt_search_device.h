@@ -14,17 +14,29 @@
 namespace diee {
 namespace ttt {
 
-// One node, 32 bytes.  A game's nodes are a slab of 10 + 8 * iterations of them (the root, at most 9 root children, at most one expansion
-// of at most 8 children per iteration); the children of a node are contiguous, first_child + j in ascending cell order, like the host Store.
-struct SearchNode {
+// A node of a game's tree, 16 bytes.  The children of a node are contiguous, first_child + j in ascending cell order like the host Store: a
+// child's action and state follow from the parent's state (child j is the j-th empty cell) and the path of a descent is written down, so
+// neither is stored.
+struct RunNode {
     float visits, value, prior;
-    uint32_t state;            // 2 bits per cell (0 empty, 1 = +1, 3 = -1) in bits 0 .. 17, bit 18 = the player to move is +1
-    int32_t parent, first_child;
-    uint32_t meta;             // n_children | action << 8 | drained << 16
-    uint32_t pad;
+    uint32_t link;             // first_child | n_children << 20 | drained << 24
 };
-static_assert(sizeof(SearchNode) == 32, "two 16-byte loads per child");
-constexpr uint32_t kMetaDrained = 1u << 16;
+static_assert(sizeof(RunNode) == 16, "one 16-byte load per child");
+constexpr uint32_t kRunDrained = 1u << 24;
+// The most nodes a game's tree can hold after `iterations` iterations: a game's slab.  Level d of a tic-tac-toe tree has at most
+// 9 * 8 * .. * (10 - d) nodes, each with at most 9 - d children; the root is expanded before the first iteration and an iteration expands at
+// most one node.  The sum is largest when the expansions go to the shallowest levels first: 9 nodes of 8 children, 72 of 7, 504 of 6, ...
+// (369 at 50.)  It stops at the whole game tree, so first_child fits the 20 bits of the link word whatever the iterations.
+constexpr uint32_t run_node_bound(uint32_t iterations) {
+    uint32_t nodes = 10, level = 9;
+    for (uint32_t d = 1; d < 9 && iterations != 0; ++d) {
+        const uint32_t e = iterations < level ? iterations : level;
+        nodes += e * (9 - d); iterations -= e; level *= 9 - d;
+    }
+    return nodes;
+}
+static_assert(run_node_bound(0) == 10 && run_node_bound(9) == 82 && run_node_bound(50) == 369 && run_node_bound(0xFFFFFFFFu) == 986410, "");
+static_assert(run_node_bound(0xFFFFFFFFu) < (1u << 20), "RunNode::link keeps first_child in 20 bits");
 constexpr int kPathCap = 10;   // root + 9 plies
 
 // What a game carries from launch to launch.
@@ -38,7 +50,7 @@ struct SearchGame {
     uint32_t expansions, children, max_children, selections, depth_sum, terminal_hits;     // diee_stats, this game's share
     uint32_t ever;             // 0 until this slot selects for the first time: till then `sel` names node 0 of the ONE NodeStore, game 0's root
     float root_value;          // the evaluation of the root's state (what a slot that never selected backpropagates under the quirks)
-    uint32_t pad;
+    uint32_t root_state;       // the packed word of ttt_rules_device.h
     int32_t path[kPathCap];
     uint32_t pad2[2];
 };
@@ -49,7 +61,7 @@ enum { kCntExpansions, kCntChildren, kCntMaxChildren, kCntSelections, kCntDepthS
 struct SearchParams {
     NetParams net;
     const diee_ttt_state* roots;
-    SearchNode* nodes;                 // [n][slab]
+    RunNode* nodes;                    // [n][slab], slab = run_node_bound(iterations); unused by k_ttt_search_run with its tree in LDS
     SearchGame* games;                 // [n]
     uint32_t* any_selected;            // [iterations]: word k is set by launch k if any game selected a leaf that needs the network
     uint32_t* never_selected;          // [iterations]: word k counts the games other than game 0 that have not selected once up to launch k
@@ -66,26 +78,6 @@ struct SearchParams {
 void launch_ttt_search(hipStream_t st, const SearchParams& P);
 
 // ---- k_ttt_search_run: the whole search of a workgroup's 16 games in one launch ------------------------------------------------------------------
-// A node of its tree, 16 bytes: a child's action and state follow from the parent's state (child j is the j-th empty cell in ascending
-// order) and the path of a descent is written down, so neither is stored.
-struct RunNode {
-    float visits, value, prior;
-    uint32_t link;             // first_child | n_children << 16 | drained << 20
-};
-static_assert(sizeof(RunNode) == 16, "one 16-byte load per child");
-constexpr uint32_t kRunDrained = 1u << 20;
-// The most nodes a game's tree can hold after `iterations` iterations.  Level d of a tic-tac-toe tree has at most 9 * 8 * .. * (10 - d)
-// nodes, each with at most 9 - d children; the root is expanded before the first iteration and an iteration expands at most one node.  The
-// sum is largest when the expansions go to the shallowest levels first: 9 nodes of 8 children, 72 of 7, 504 of 6, ...  (369 at 50.)
-constexpr uint32_t run_node_bound(uint32_t iterations) {
-    uint32_t nodes = 10, level = 9;
-    for (uint32_t d = 1; d < 9 && iterations != 0; ++d) {
-        const uint32_t e = iterations < level ? iterations : level;
-        nodes += e * (9 - d); iterations -= e; level *= 9 - d;
-    }
-    return nodes;
-}
-static_assert(run_node_bound(0) == 10 && run_node_bound(9) == 82 && run_node_bound(50) == 369 && run_node_bound(0xFFFFFFFFu) == 986410, "");
 // The tree stays in LDS while the 16 games' bounds fit into what the network's 62400 bytes (NetLds) and the kernel's own 1280 leave of a
 // CU's 160 KB; above that it lies in the HBM slab.  kRunLdsIters is the largest `iterations` of the LDS placement.
 constexpr uint32_t kRunLdsBytes = 160 * 1024 - 62400 - 1280;
@@ -96,8 +88,8 @@ constexpr uint32_t run_lds_iters() {
 }
 constexpr uint32_t kRunLdsIters = run_lds_iters();
 constexpr uint32_t kRunMaxIters = 4096;            // k_ttt_vanilla's bound: a launch stays far below a second
-// ttt_search_run_kernels.hip: ceil(n / 16) workgroups; P.k is unused, P.slab = run_node_bound(iterations), P.nodes (RunNode [n][slab]) only
-// if !lds_tree.  `first`: no launch with the tree in LDS has been made on this device yet (the dynamic LDS has to be asked for once).
+// ttt_search_run_kernels.hip: ceil(n / 16) workgroups; P.k is unused, P.nodes only if !lds_tree.  `first`: no launch with the tree in LDS
+// has been made on this device yet (the dynamic LDS has to be asked for once).
 hipError_t launch_ttt_search_run(hipStream_t st, const SearchParams& P, bool lds_tree, bool first);
 
 // The buffers of the device search, owned by the ctx, grown by doubling; results of one call in page-locked memory.

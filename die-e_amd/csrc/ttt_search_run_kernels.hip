@@ -13,22 +13,19 @@
 // Where a game lives.  Row (sel, fresh, n_nodes, depth, sel_state, ever, the counters) and the path (lane j keeps the node at depth j) stay
 //   in registers from the first step to the last; SearchGame is not used.  The policy row and value that an evaluation hands to the next
 //   phase A go through s_eval, 16 x 10 floats of LDS.
-// Tree.  RunNode, 16 bytes: visits, value, prior and one link word; a level of a descent is one 16-byte load per lane, and the child's state
-//   is derived: child j is the j-th empty cell of the parent's state.  A game's slab is run_node_bound(iterations) nodes.  LDS_TREE: the 16
-//   slabs are dynamic LDS behind the network's 62 KB (iterations <= kRunLdsIters); else they lie in HBM (P.nodes).
-// Step k = 0 .. iterations, phases divided by workgroup barriers, with the meaning of k_ttt_search's launch k:
+// Tree.  k_ttt_search's RunNodes, a slab of run_node_bound(iterations) per game.  LDS_TREE: the 16 slabs are dynamic LDS behind the network's
+//   62 KB (iterations <= kRunLdsIters); else they lie in HBM (P.nodes).
+// Step k = 0 .. iterations (run_steps of ttt_search_run_device.h: k_ttt_selfplay_run of ttt_selfplay_kernels.hip inlines it too), phases
+// divided by workgroup barriers, with the meaning of k_ttt_search's launch k and the same pieces of ttt_search_iter_device.h:
 //   C  net_eval on the states of sel of the 16 games (k = 0: the roots; the ONE Dirichlet sample is mixed in), policy and value to s_eval.
 //      Skipped, uniformly over the workgroup, when none of its games selected in the iteration before: without the quirks nothing reads
 //      a stale row, with them (one workgroup) this is the reference's `continue`.
-//   A  k = 0: root visits = 1, expand the root.  k >= 1: finish iteration k - 1 as k_ttt_search does, any_selected / never_selected of that
-//      iteration being the workgroup's own words.
-//   B  k < iterations: descend by PUCT (puct() and the chain `if (!(ub > un))` of k_ttt_search, operation for operation), backpropagate
-//      a finished game at once, else the leaf becomes sel.  A workgroup that selected ORs any_selected[k] in HBM: the host derives nn_evals
-//      from those words after the kernel has ended; the kernel never reads them.
-//   after A of step `iterations`: root probabilities, n_children, root_visits, the counters, as k_ttt_search writes them.
+//   A  k = 0: start_search.  k >= 1: finish_iteration, any_selected / never_selected of iteration k - 1 being the workgroup's own words.
+//   B  k < iterations: descend, end_selection.  A workgroup that selected ORs any_selected[k] in HBM: the host derives nn_evals from those
+//      words after the kernel has ended; the kernel never reads them.
+//   after A of step `iterations`: run_root_row, n_children, root_visits, add_counters, as k_ttt_search writes them.
 // Everything is compiled under DIEE_TTT_NO_PK_F32 with nothing but builtins called (ttt_net_device.h says why); all stores are plain C++;
 // every loop is bounded by iterations, kPathCap or the 16 games of a workgroup.  The build must show 0 bytes of scratch.
-// The steps and the root's row are device functions of ttt_search_run_device.h: k_ttt_selfplay_run (ttt_selfplay_kernels.hip) inlines them too.
 #include <hip/hip_runtime.h>
 
 #include "ttt_net_device.h"
@@ -53,44 +50,21 @@ __global__ __launch_bounds__(256) DIEE_TTT_NO_PK_F32 void k_ttt_search_run(Searc
     const bool valid = gi < P.n;
     RunNode* nodes;
     if constexpr (LDS_TREE) nodes = (RunNode*)s_tree + (size_t)grp * P.slab;
-    else nodes = (RunNode*)P.nodes + (valid ? gi : 0) * P.slab;
+    else nodes = P.nodes + (valid ? gi : 0) * P.slab;
 
-    uint32_t root_state = 0u;                                        // a game past n is the empty board, computed and not stored
-    if (valid) {
-        const uint32_t* r = (const uint32_t*)(P.roots + gi);
-        const uint32_t w0 = r[0], w1 = r[1], w2 = r[2];
-#pragma unroll
-        for (int cidx = 0; cidx < 9; ++cidx) {
-            const uint32_t w = cidx < 4 ? w0 : cidx < 8 ? w1 : w2;
-            root_state |= pack_cell((int)(signed char)(w >> (8 * (cidx & 3))), cidx);
-        }
-        if ((signed char)(w2 >> 8) > 0) root_state |= 1u << 18;
-    }
+    const uint32_t root_state = valid ? unpack_root(P.roots + gi) : 0u;      // a game past n is the empty board, computed and not stored
     Row R;
 #pragma unroll
     for (int i = 0; i < kCntCount; ++i) R.cnt[i] = 0u;
     run_steps(P, P.noise, P.any_selected, S, s_eval, s_any, s_never, nodes, valid, gi, root_state, tid, R);
 
-    // ---- the results: get_prob_tensor_parallel (utils.rs:42-58), the root's counts, the statistics -------------------------------------------------
+    // ---- the results ------------------------------------------------------------------------------------------------------------------------
     uint32_t nc;
     float root_visits;
     const float prob = run_root_row(nodes, valid, root_state, j, row0, nc, root_visits);
     if (valid && j < 9) P.probs[gi * 9 + j] = prob;
-    if (j == 0) {
-        if (valid) { P.n_children[gi] = nc; P.root_visits[gi] = root_visits; }
-#pragma unroll
-        for (int i = 0; i < kCntCount; ++i) s_cnt[grp][i] = valid ? R.cnt[i] : 0u;
-    }
-    group_barrier();
-    if (tid < kCntCount) {
-        unsigned long long t = 0;
-        for (int g = 0; g < kB; ++g) {
-            const unsigned long long v = s_cnt[g][tid];
-            t = tid == kCntMaxChildren ? (v > t ? v : t) : t + v;
-        }
-        if (tid == kCntMaxChildren) __hip_atomic_fetch_max(P.counters + tid, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else __hip_atomic_fetch_add(P.counters + tid, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (valid && j == 0) { P.n_children[gi] = nc; P.root_visits[gi] = root_visits; }
+    add_counters(s_cnt, P.counters, valid, R, tid);
 }
 
 hipError_t launch_ttt_search_run(hipStream_t st, const SearchParams& P, bool lds_tree, bool first) {

@@ -92,7 +92,7 @@ void DeviceSelfPlay::run(uint32_t n_games, uint32_t first_game_id, const diee_mc
 
     SpParams P{};
     P.sp.net = net_.params();
-    P.sp.nodes = (SearchNode*)d_nodes_;
+    P.sp.nodes = (RunNode*)d_nodes_;
     P.sp.n = n_games; P.sp.iterations = cfg.iterations; P.sp.slab = run_node_bound(cfg.iterations); P.sp.quirks = 0u;
     P.sp.c = cfg.c; P.sp.eps = cfg.dir_eps; P.sp.one_minus_eps = 1.0f - cfg.dir_eps;
     P.head = (SpHead*)d_head_;

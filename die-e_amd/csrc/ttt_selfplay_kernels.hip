@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) DIEE_TTT_NO_PK_F32 void k_ttt_selfplay_run(SpP
     const bool valid = gi < P.sp.n;
     RunNode* nodes;
     if constexpr (LDS_TREE) nodes = (RunNode*)s_tree + (size_t)grp * P.sp.slab;
-    else nodes = (RunNode*)P.sp.nodes + (valid ? gi : 0) * P.sp.slab;
+    else nodes = P.sp.nodes + (valid ? gi : 0) * P.sp.slab;
 
     if (j == 0) {                                                    // TicTacToe::new, mod.rs:28-30: the empty board, -1 to move
 #pragma unroll

@@ -56,6 +56,22 @@ def test_mcts_batch_equals_the_host_search(eng, n, quirks, iters, c):
         assert d["stats"][key] == h["stats"][key], key
 
 
+def test_a_tree_past_65535_nodes_equals_the_host_search(eng):
+    """RunNode::link keeps first_child in 20 bits: one empty-board root searched until its node indices pass 16 bits.  At c = 2.0 the tree
+    stops growing near 13 000 children (the host search over the fp32 host network: 12 401 at 15 000 iterations, 13 019 at 40 000: the
+    descents end on finished games), at c = 8.0 near 47 000 (45 797 at 20 000, 47 006 at 40 000); c = 32.0 gave 99 612 at 30 000."""
+    roots, cfg = diee_amd.ttt_new(1), _cfg(30000, 32.0)
+    eng.set_option("search", "host")
+    h = eng.alpha_mcts_parallel(roots, cfg, 5, 2, ref_quirks=False)
+    assert h["stats"]["children"] >= 65536                                  # children + 1 = the tree's nodes: the case does not pass empty
+    eng.set_option("search", "device")
+    d = eng.alpha_mcts_parallel(roots, cfg, 5, 2, ref_quirks=False)
+    for key in ("probs", "root_visits", "n_children"):
+        assert np.array_equal(d[key], h[key], equal_nan=True), key
+    for key in KEYS:
+        assert d["stats"][key] == h["stats"][key], key
+
+
 @pytest.mark.parametrize("quirks", [1, 0])
 def test_self_play_equals_the_host_search(eng, quirks):
     out = {}
