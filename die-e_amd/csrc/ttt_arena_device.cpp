@@ -1,10 +1,12 @@
-// ttt_arena_device.cpp -- host side of the tic-tac-toe device arena (ttt_arena_device.h): buffers, the round loop, the one copy-out.
+// ttt_arena_device.cpp -- host side of the tic-tac-toe device arena (ttt_arena_device.h): buffers, the round loop or the one launch of
+// k_ttt_arena_run, the one copy-out.
 #include "ttt_arena_device.h"
 
 #include <chrono>
 #include <cstring>
 
 #include "engine.h"
+#include "search_host.h"
 
 namespace diee {
 namespace ttt {
@@ -25,7 +27,109 @@ DeviceArena::~DeviceArena() {
 
 void DeviceArena::release() {
     drop(d_out_, false); drop(h_out_, true); drop(d_work_, false); drop(h_counts_, true);
-    cap_ = 0;
+    drop(d_run_, false); drop(h_run_, true); drop(d_nodes_, false);
+    cap_ = 0; cap_run_ = 0; cap_nodes_ = 0;
+}
+
+// k_ttt_arena_run has k_ttt_search_run's registers: one workgroup per CU.  A call of more workgroups than CUs would run in passes, each
+// pass as long as its longest game; it goes to the round loop, whose searches shrink as games retire.
+bool DeviceArena::serves(const ArenaArgs& a) {
+    if (search_.fused_level() != 2 || a.cfg.iterations > kRunMaxIters) return false;
+    for (int s = 0; s < 2; ++s) {
+        if (a.agents[s] != DIEE_AGENT_MODEL && a.agents[s] != DIEE_AGENT_RANDOM) return false;      // k_ttt_vanilla is no device function of the family
+        if (a.agents[s] == DIEE_AGENT_MODEL && (a.flags[s] & DIEE_FLAG_REF_QUIRKS) != 0) return false;      // Q14 couples the slots of a search
+    }
+    int cus = 0, lds = 0;
+    search_.limits(cus, lds);
+    return arena_run_groups(a.n_games) <= (uint32_t)cus;
+}
+
+// As reserve(): a buffer that has to grow is freed first and its capacity cleared.
+void DeviceArena::reserve_run(size_t bytes, size_t nodes) {
+    if (bytes <= cap_run_ && nodes <= cap_nodes_) return;
+    HIPCHK(hipStreamSynchronize(net_.stream()));
+    if (bytes > cap_run_) {
+        size_t cap = 64 * 1024;
+        while (cap < bytes) cap *= 2;
+        drop(d_run_, false); drop(h_run_, true);
+        cap_run_ = 0;
+        HIPCHK(hipMalloc(&d_run_, cap));
+        HIPCHK(hipHostMalloc(&h_run_, cap));
+        cap_run_ = cap;
+    }
+    if (nodes > cap_nodes_) {
+        size_t cap = 64 * 1024;
+        while (cap < nodes) cap *= 2;
+        drop(d_nodes_, false);
+        cap_nodes_ = 0;
+        HIPCHK(hipMalloc(&d_nodes_, cap * sizeof(RunNode)));
+        cap_nodes_ = cap;
+    }
+}
+
+bool DeviceArena::run_one_launch(const ArenaArgs& a, diee_arena_result* res, int8_t* winner, uint32_t* retired_round, int8_t* retired_side,
+                                 diee_ttt_state* final_states, diee_stats* stats) {
+    const uint32_t n = a.n_games, iters = a.cfg.iterations;
+    bool any_model = false;
+    for (int s = 0; s < 2; ++s) any_model = any_model || a.agents[s] == DIEE_AGENT_MODEL;
+    HIPCHK(hipSetDevice(net_.device()));
+    int cus = 0, lds = 0;
+    search_.limits(cus, lds);
+    const bool lds_tree = iters <= kRunLdsIters && lds >= 160 * 1024;
+    const size_t head = sizeof(ArHead) + (size_t)2 * kArRounds * iters * 4, bytes = head + (size_t)n * (4 + 4 + 1 + 1);
+    try { reserve_run(bytes, any_model && !lds_tree ? (size_t)n * run_node_bound(iters) : 0); } catch (...) { (void)hipGetLastError(); throw; }
+    hipStream_t stream = net_.stream();
+
+    ArParams P{};
+    P.sp.nodes = (RunNode*)d_nodes_;
+    P.sp.n = n; P.sp.iterations = iters; P.sp.slab = run_node_bound(iters); P.sp.quirks = 0u;
+    P.sp.c = a.cfg.c; P.sp.eps = a.cfg.dir_eps; P.sp.one_minus_eps = 1.0f - a.cfg.dir_eps;
+    unsigned char* o = (unsigned char*)d_run_;
+    P.head = (ArHead*)o;
+    P.any_selected = (uint32_t*)(o + sizeof(ArHead));
+    P.state = (uint32_t*)(o + head);
+    P.retired_round = P.state + n;
+    P.winner = (int8_t*)(P.retired_round + n);
+    P.retired_side = P.winner + n;
+    P.seed = a.seed; P.round_limit = a.round_limit; P.inv_t = (float)(1.0 / (double)a.temperature);
+    P.rounds = a.max_rounds != 0 && a.max_rounds < kArRounds ? a.max_rounds : kArRounds;
+    for (uint32_t s = 0; s < 2; ++s) {
+        P.agents[s] = a.agents[s];
+        if (a.agents[s] != DIEE_AGENT_MODEL) continue;
+        P.nets[s] = *a.nets[s];
+        for (uint32_t r = 0; r < P.rounds; ++r) dirichlet_host(a.seed, 2 * r + s, a.cfg.dir_alpha, A, P.noise[2 * r + s]);      // as DeviceSearch::enqueue for (seed, step)
+    }
+
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemsetAsync(d_run_, 0, head, stream));
+    HIPCHK(launch_ttt_arena_run(stream, P, lds_tree, lds_tree && !lds_asked_));
+    lds_asked_ = lds_asked_ || lds_tree;
+    HIPCHK(hipMemcpyAsync(h_run_, d_run_, bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+
+    const unsigned char* h = (const unsigned char*)h_run_;
+    const ArHead* H = (const ArHead*)h;
+    if (H->alive != 0u && (a.max_rounds == 0 || a.max_rounds > kArRounds)) return false;       // skipped turns: the round loop plays the call
+    const uint32_t* flag = (const uint32_t*)(h + sizeof(ArHead));
+    unsigned long long tot[kTaWords];
+    memcpy(tot, H->totals, sizeof tot);
+    uint64_t move_steps[2] = {0, 0};
+    uint32_t rounds = P.rounds;
+    for (uint32_t r = P.rounds; r-- > 0;) {
+        if (H->live[2 * r] + H->live[2 * r + 1] == 0u) rounds = r;                            // the first round with nobody alive
+        for (uint32_t s = 0; s < 2; ++s) {
+            const uint32_t step = 2 * r + s;
+            if (a.agents[s] != DIEE_AGENT_MODEL || H->live[step] == 0u) continue;
+            uint64_t evals = 1;                                                                // the roots, then one per iteration somebody selected in
+            for (uint32_t k = 0; k < iters; ++k) evals += flag[(size_t)step * iters + k] != 0u;
+            tot[(size_t)s * kTaPlayerWords + kTaNnEvals] += evals * H->live[step];
+            move_steps[s] += 1;
+        }
+    }
+    last_launches_ = 1;
+    decode(a, tot, (const uint32_t*)(h + head), move_steps, rounds, secs, res, winner, retired_round, retired_side, final_states, stats);
+    return true;
 }
 
 // As the searches' buffers: freed before they grow, so a failed allocation leaves the ctx consistent and nothing has been launched.
@@ -74,6 +178,7 @@ void DeviceArena::run(const ArenaArgs& a, diee_arena_result* res, int8_t* winner
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t n_live = n, round = 0;
     uint64_t searches[2] = {0, 0};
+    uint32_t launches = 0;                                                // search-kernel launches: option arena_last_launches
     for (;;) {                                                            // versus.rs:191
         launch_ttt_arena_split(stream, G, n_live, round);                 // :195-196
         HIPCHK(hipGetLastError());
@@ -92,10 +197,10 @@ void DeviceArena::run(const ArenaArgs& a, diee_arena_result* res, int8_t* winner
             if (a.agents[s] == DIEE_AGENT_MODEL) {                        // :279-283
                 const DeviceSearch::Enqueued E = search_.enqueue(roots, cnt[s], *a.nets[s], a.cfg, a.seed, 2 * round + s, quirks);
                 M.probs = E.probs; M.n_children = E.n_children; M.counters = E.counters; M.any_selected = E.any_selected;
-                ++searches[s];
+                ++searches[s]; launches += search_.last_launches();
             } else if (a.agents[s] == DIEE_AGENT_MCTS) {                  // :303-306
                 M.vout = vanilla_.enqueue(roots, keys, cnt[s], a.cfg, a.seed, quirks);
-                ++searches[s];
+                ++searches[s]; launches += 1;
             }
             launch_ttt_arena_move(stream, G, M, a.agents[s]);             // :220-266
             HIPCHK(hipGetLastError());
@@ -108,10 +213,19 @@ void DeviceArena::run(const ArenaArgs& a, diee_arena_result* res, int8_t* winner
 
     const unsigned char* h = (const unsigned char*)h_out_;
     const unsigned long long* tot = (const unsigned long long*)h;
-    const uint32_t* state = (const uint32_t*)(h + kTaWords * sizeof(unsigned long long));
+    if (tot[kTaOverflow]) throw EngineError(DIEE_ERR_CAPACITY, "k_ttt_vanilla: a game's slab is full");
+    last_launches_ = launches;
+    decode(a, tot, (const uint32_t*)(h + kTaWords * sizeof(unsigned long long)), searches, round, secs, res, winner, retired_round, retired_side,
+           final_states, stats);
+}
+
+// the outputs of diee_ttt_arena from the call's totals and its per-game block: state | retired_round | winner | retired_side
+void DeviceArena::decode(const ArenaArgs& a, const unsigned long long* tot, const uint32_t* state, const uint64_t move_steps[2], uint32_t rounds, double secs,
+                         diee_arena_result* res, int8_t* winner, uint32_t* retired_round, int8_t* retired_side, diee_ttt_state* final_states,
+                         diee_stats* stats) {
+    const uint32_t n = a.n_games;
     const uint32_t* rr = state + n;
     const int8_t* win = (const int8_t*)(rr + n);
-    if (tot[kTaOverflow]) throw EngineError(DIEE_ERR_CAPACITY, "k_ttt_vanilla: a game's slab is full");
     if (winner) memcpy(winner, win, n);
     if (retired_round) memcpy(retired_round, rr, (size_t)n * sizeof(uint32_t));
     if (retired_side) memcpy(retired_side, win + n, n);
@@ -127,7 +241,7 @@ void DeviceArena::run(const ArenaArgs& a, diee_arena_result* res, int8_t* winner
         for (int s = 0; s < 2; ++s) {
             const unsigned long long* t = tot + (size_t)s * kTaPlayerWords;
             diee_stats& st = stats[s];
-            st.plies = t[kTaPlies]; st.fragments = t[kTaMoves]; st.games = t[kTaRetired]; st.move_steps = searches[s]; st.seconds = secs;
+            st.plies = t[kTaPlies]; st.fragments = t[kTaMoves]; st.games = t[kTaRetired]; st.move_steps = move_steps[s]; st.seconds = secs;
             st.nn_evals = t[kTaNnEvals]; st.nn_rows = t[kTaNnEvals]; st.expansions = t[kTaExpansions]; st.children = t[kTaChildren];
             st.max_children = t[kTaMaxChildren]; st.selections = t[kTaSelections]; st.depth_sum = t[kTaDepthSum]; st.terminal_hits = t[kTaTerminal];
         }
@@ -135,7 +249,7 @@ void DeviceArena::run(const ArenaArgs& a, diee_arena_result* res, int8_t* winner
     if (res) {
         memset(res, 0, sizeof *res);
         res->wins_p1 = (uint32_t)tot[kTaWins1]; res->wins_p2 = (uint32_t)tot[kTaWins2]; res->draws = (uint32_t)tot[kTaDraws];
-        res->rounds = round; res->seconds = secs;
+        res->rounds = rounds; res->seconds = secs;
     }
 }
 

@@ -18,6 +18,7 @@
 //            rounding's leftovers the last non-zero one.  A root without children or a zero total skips the turn.
 //   Random   the row's ballot of empty cells; the min(int(u * count), count - 1)-th set bit.
 //   Mcts     the move k_ttt_vanilla left in its VanillaOut; 10 skips the turn.
+//   (model_move, random_move and play_turn of ttt_arena_move_device.h: k_ttt_arena_run of ttt_arena_run_kernels.hip calls them too)
 //   then lane 0 applies the move, looks for a winner or a full board, applies the round limit, retires the game; a skipped turn only flips
 //   the player.  The turn's counts (and an Mcts search's per-game counters) are reduced over the 16 rows in LDS and added once per
 //   workgroup to the call's totals; workgroup 0 of a Model turn also adds the search's counters and the rows it evaluated, (1 + the
@@ -29,6 +30,7 @@
 
 #include "bg_device.h"
 #include "ttt_arena_device.h"
+#include "ttt_arena_move_device.h"
 #include "ttt_net_device.h"
 #include "ttt_rules_device.h"
 
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(256) DIEE_TTT_NO_PK_F32 void k_ttt_arena_move(Arena
     uint32_t red[kRedCount];
 #pragma unroll
     for (int i = 0; i < kRedCount; ++i) red[i] = 0u;
-    int move = 10;                                                                     // TicTacToe::EMPTY_MOVE
+    int move = kEmptyMove;
     if (AGENT == DIEE_AGENT_MCTS) {                                                    // :303-306
         const VanillaOut* O = M.vout + slot;
         move = (int)O->move;
@@ -126,41 +128,19 @@ __global__ __launch_bounds__(256) DIEE_TTT_NO_PK_F32 void k_ttt_arena_move(Arena
         red[kRedDepthSum] = O->cnt[kVcDepthSum]; red[kRedOverflow] = O->overflow;
     } else {
         const double u = draw_uniform(M.seed, g, M.round, kTagSample, 0u);
-        if (AGENT == DIEE_AGENT_MODEL) {                                               // :279-299
-            const float x = j < 9 ? M.probs[slot * 9 + (size_t)j] : 0.f;
-            const float w = det_powf(x > 0.f ? x : 0.f, M.inv_t);                      // (NaN, the row of a childless root: 0)
-            double total;
-            const int pick = weighted_pick(w, u, row0, total);
-            if (M.n_children[slot] != 0u && total > 0.0) move = pick;                  // :286-293: else EMPTY_MOVE
-        } else {                                                                       // :308-317
-            const uint32_t mask = row_ballot(j < 9 && cell_of(st, j < 9 ? j : 0) == 0, row0);
-            const int count = __builtin_popcount(mask);
-            int idx = (int)(u * (double)count);
-            idx = idx > count - 1 ? count - 1 : idx;
-            int seen = 0;
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                const bool set = (mask >> c) & 1u;
-                if (set && seen == idx) move = c;
-                seen += set ? 1 : 0;
-            }
-        }
+        if (AGENT == DIEE_AGENT_MODEL) move = model_move(j < 9 ? M.probs[slot * 9 + (size_t)j] : 0.f, M.n_children[slot], M.inv_t, u, row0);      // :279-299
+        else move = random_move(st, u, j, row0);                                       // :308-317
     }
     if (valid && j == 0) {
+        bool moved, retired;
+        int w;
+        G.state[g] = play_turn(st, move, M.round, M.round_limit, moved, retired, w);   // :225-237
         red[kRedPlies] = 1u;
-        if (move > 8) {                                                                // :225-228 skip_turn; continue
-            G.state[g] = st ^ (1u << 18);
-        } else {
-            st = apply_move(st, move);                                                 // :230
-            G.state[g] = st;
-            red[kRedMoves] = 1u;
-            int w;
-            const bool over = finished(st, w);
-            if (over || M.round + 1u >= M.round_limit) {                               // :233-237 (round_count was incremented at :219)
-                G.winner[g] = (int8_t)w; G.retired_round[g] = M.round; G.retired_side[g] = (int8_t)M.side;
-                red[kRedRetired] = 1u;
-                red[w < 0 ? kRedWins1 : w > 0 ? kRedWins2 : kRedDraws] = 1u;
-            }
+        red[kRedMoves] = moved ? 1u : 0u;
+        if (retired) {
+            G.winner[g] = (int8_t)w; G.retired_round[g] = M.round; G.retired_side[g] = (int8_t)M.side;
+            red[kRedRetired] = 1u;
+            red[w < 0 ? kRedWins1 : w > 0 ? kRedWins2 : kRedDraws] = 1u;
         }
     }
     if (j == 0) {

@@ -106,7 +106,7 @@ Engine::~Engine() = default;
 
 namespace {
 [[noreturn]] void unsupported_option(const std::string& key) {
-    throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has the options `nn`, `search`, `search_fused` and the read-only `search_last_launches`, `self_play_last_launches` and `search_fused_lds_iters`; `" + key + "` belongs to a backgammon ctx");
+    throw EngineError(DIEE_ERR_UNSUPPORTED, "a tic-tac-toe ctx has the options `nn`, `search`, `search_fused` and the read-only `search_last_launches`, `self_play_last_launches`, `arena_last_launches` and `search_fused_lds_iters`; `" + key + "` belongs to a backgammon ctx");
 }
 }  // namespace
 
@@ -127,7 +127,7 @@ void Engine::set_option(const std::string& key, const std::string& value) {
         if (dsearch_) dsearch_->set_fused((uint32_t)(value[0] - '0'));
         return;
     }
-    if (key == "search_last_launches" || key == "self_play_last_launches" || key == "search_fused_lds_iters") throw EngineError(DIEE_ERR_ARG, "option " + key + " is read-only");
+    if (key == "search_last_launches" || key == "self_play_last_launches" || key == "arena_last_launches" || key == "search_fused_lds_iters") throw EngineError(DIEE_ERR_ARG, "option " + key + " is read-only");
     if (key != "nn") unsupported_option(key);
     if (value == "host") {
         if (dsearch_) throw EngineError(DIEE_ERR_ARG, "option nn = host while option search is `device`: set search = host first");
@@ -145,6 +145,7 @@ std::string Engine::get_option(const std::string& key) const {
     if (key == "search_fused") return std::to_string(dsearch_ ? dsearch_->fused_level() : 0u);
     if (key == "search_last_launches") return std::to_string(dsearch_ ? dsearch_->last_launches() : 0u);
     if (key == "self_play_last_launches") return std::to_string(dsearch_ ? dsearch_->self_play_launches() : 0u);
+    if (key == "arena_last_launches") return std::to_string(darena_ ? darena_->last_launches() : 0u);
     if (key == "search_fused_lds_iters") return std::to_string(kRunLdsIters);
     if (key != "nn") unsupported_option(key);
     return dev_ ? "device" : "host";
@@ -626,6 +627,8 @@ void Engine::arena(const Engine* e1, int agent1, const Engine* e2, int agent2, u
             a.nets[s] = agents[s] == DIEE_AGENT_MODEL ? &eng[s]->dev_->params() : nullptr;
         }
         a.n_games = n_games; a.cfg = cfg; a.temperature = temperature; a.seed = seed; a.round_limit = round_limit; a.max_rounds = max_rounds;
+        // option search_fused = 2: the whole call is one launch of k_ttt_arena_run (ttt_arena_device.h), unless a game outlasts its nine rounds
+        if (darena_->serves(a) && darena_->run_one_launch(a, res, winner, retired_round, retired_side, final_states, stats)) return;
         darena_->run(a, res, winner, retired_round, retired_side, final_states, stats);
         return;
     }

@@ -62,8 +62,9 @@ public:
     // and every move-step of self_play, and k_ttt_vanilla (ttt_vanilla_device.h) behind mcts_vanilla_batch.  "device" needs "nn" = "device" (else DIEE_ERR_ARG), and "nn" cannot go back to "host" before "search" has.
     // option "search_fused": "0" (default) | "1" = an eligible device search is ONE launch of k_ttt_search_run (ttt_search_device.h); "1" needs
     // "search" = "device" (else DIEE_ERR_ARG) and "search" = "host" resets it.  "2" = "1", and a self_play call without the quirks whose
-    // workgroups have a CU each is ONE launch of k_ttt_selfplay_run plus the delivery (ttt_selfplay_device.h).  Read-only: "search_last_launches",
-    // "self_play_last_launches" (the search launches of the last self_play), "search_fused_lds_iters".
+    // workgroups have a CU each is ONE launch of k_ttt_selfplay_run plus the delivery (ttt_selfplay_device.h), and an arena call of
+    // Model and Random players without the quirks is ONE launch of k_ttt_arena_run (ttt_arena_device.h).  Read-only: "search_last_launches",
+    // "self_play_last_launches" (the search launches of the last self_play), "arena_last_launches" (of the last arena), "search_fused_lds_iters".
     // Every other key: DIEE_ERR_UNSUPPORTED.
     void set_option(const std::string& key, const std::string& value);
     std::string get_option(const std::string& key) const;
@@ -84,7 +85,7 @@ public:
                             float* child_values, diee_vanilla_stats* stats) const;
     // play::<TicTacToe> (versus.rs:160-318): diee_ttt_arena of include/diee.h, called on the hosting ctx (e1, or e2 when e1 is null).  Option
     // "search" of the hosting ctx names the path: "host" = the round loop of ttt_host.cpp over each player's own searches, "device" = every round
-    // on this ctx's stream (ttt_arena_device.h).
+    // on this ctx's stream, or the whole call in one launch under "search_fused" = "2" (ttt_arena_device.h).
     void arena(const Engine* e1, int agent1, const Engine* e2, int agent2, uint32_t n_games, const diee_mcts_cfg& cfg, float temperature, uint64_t seed,
                uint32_t round_limit, uint32_t max_rounds, const uint32_t flags[2], diee_arena_result* res, int8_t* winner, uint32_t* retired_round,
                int8_t* retired_side, diee_ttt_state* final_states, diee_stats* stats) const;

@@ -231,13 +231,22 @@ diee_status diee_device_pci_bus_id(int device, char* out /*[cap], >= 16*/, size_
  *                                 most 4096 iterations and of at most 16 games per CU, is ONE launch of k_ttt_selfplay_run -- a workgroup carries
  *                                 its 16 games from the empty board to their last move: search, sampling, the records, the rules -- and two
  *                                 small delivery kernels; same records and statistics, bit for bit.  Every other diee_self_play call keeps the
- *                                 host loop over one search per move-step.  "1" and "2" are accepted only while "search" is "device" (else
+ *                                 host loop over one search per move-step.  Under "2" on the hosting ctx a diee_ttt_arena call of Model and
+ *                                 Random players, no DIEE_FLAG_REF_QUIRKS on a Model side, at most 4096 iterations and no more workgroups (16
+ *                                 games of one half of the call each) than the device has CUs is ONE launch of k_ttt_arena_run -- a workgroup
+ *                                 carries its 16 games from the empty board to their retirement, the two sides' workgroups side by side --;
+ *                                 same outputs and statistics, bit for bit.  It plays nine rounds; a call in which a game outlasts them
+ *                                 (skipped turns) and may go on is played again, whole, on the round loop, which every other call keeps.
+ *                                 "1" and "2" are accepted only while "search" is "device" (else
  *                                 DIEE_ERR_ARG), any other value is DIEE_ERR_ARG, and "search" = "host" resets it.  Default "0".
  *   search_last_launches  READ-ONLY, tic-tac-toe ctx: the search-kernel launches the ctx's last device search enqueued, iterations + 1 or 1
  *                                 (0 before the first, and on "search" = "host"; 1 after a one-launch diee_self_play)
  *   self_play_last_launches  READ-ONLY, tic-tac-toe ctx: the search-kernel launches of the ctx's last diee_self_play: the sum of
  *                                 search_last_launches over its move-steps, 1 for the one-launch call ("search_fused" = "2"), 0 before the
  *                                 first and on "search" = "host"
+ *   arena_last_launches   READ-ONLY, tic-tac-toe ctx: the search-kernel launches of the last diee_ttt_arena this ctx hosted on "search" =
+ *                                 "device": the sum over its searches on the round loop, 1 for the one-launch call ("search_fused" = "2"), 0
+ *                                 before the first and on "search" = "host"
  *   search_fused_lds_iters  READ-ONLY, tic-tac-toe ctx: the largest `iterations` whose tree k_ttt_search_run keeps in LDS (53)
  *   deliver_stage_rows, deliver_rows_per_game, nodes_per_expansion, path_cap        buffer sizes (tests)
  *   refill_record_areas   READ-ONLY (diee_get_option; setting it is DIEE_ERR_ARG): the record areas -- (round_limit + 2) x 6 KB each -- the last
@@ -530,7 +539,8 @@ void        diee_free_arena_log(diee_arena_log* log);
  * same bits.  "host" (default): a round loop on the host over each player's own searches, wherever its ctx runs them.  "device": every round on
  * the hosting ctx's stream -- the split by side, both searches (k_ttt_search, k_ttt_vanilla; player 2's over p2's network, which is only read),
  * the sampling, the moves and the totals; the host reads three words per round (the two sides' counts and the games alive) and the results
- * once.  Then every non-NULL ctx of the call must be on "search" = "device" and on the same GPU, else DIEE_ERR_ARG; a ctx without weights can be
+ * once.  With option "search_fused" = "2" on the hosting ctx an eligible call (see the option) is ONE launch of k_ttt_arena_run instead, with
+ * the same bits; option "arena_last_launches" tells which path the last call took.  On "device" every non-NULL ctx of the call must be on "search" = "device" and on the same GPU, else DIEE_ERR_ARG; a ctx without weights can be
  * (Random and Mcts players).
  * A Model agent whose ctx is NULL: DIEE_ERR_ARG, without loaded weights: DIEE_ERR_NO_WEIGHTS; n_games == 0, round_limit == 0, both ctxs NULL, cfg
  * or flags NULL: DIEE_ERR_ARG; an Mcts agent's cfg as for diee_ttt_mcts_vanilla_batch. */

@@ -10,7 +10,7 @@ timed pair is also checked to have played the same games.  Every call is synchro
 Each row is warmed up on both drivers, the two alternate rep by rep; the table gives the median and the spread, and a difference counts only
 if it exceeds that spread.  A second table is diee_ttt_arena alone with flags 0 (the quirks off), option search_fused = 0 against 1 on the
 hosting ctx: one launch of k_ttt_search per iteration against one of k_ttt_search_run per search, same games checked.  Prints the markdown
-tables and, last, one JSON line."""
+tables and, last, one JSON line.  Its third column is search_fused = 2, the whole call as ONE launch of k_ttt_arena_run."""
 import argparse
 import json
 import os
@@ -54,7 +54,7 @@ def main():
         print(rows[-1][0] + ": done", file=sys.stderr, flush=True)
     fused_rows = []
     for n in (16, 400):
-        t = {"0": [], "1": []}
+        t = {"0": [], "1": [], "2": []}
         for i in range(a.reps + 2):
             played = {}
             for k in t:
@@ -65,7 +65,7 @@ def main():
                 played[k] = (r["wins_p1"], r["wins_p2"], r["rounds"], r["final_states"].tobytes())
                 if i >= 2:
                     t[k].append(dt)
-            assert played["0"] == played["1"], "the two kernels played different games"
+            assert played["0"] == played["1"] == played["2"], "the kernels played different games"
         fused_rows.append((f"diee_ttt_arena flags 0, {n} games x 50 iterations", t))
         print(fused_rows[-1][0] + ": done", file=sys.stderr, flush=True)
     engines[0].set_option("search_fused", "0")
@@ -73,16 +73,18 @@ def main():
     lines = ["| arena | play_tictactoe, ms: median (min .. max) | play_tictactoe_device, ms: median (min .. max) | python / device |", "|---|---|---|---|"]
     for what, t in rows:
         lines.append(f"| {what} | {ms(t['python'])} | {ms(t['device'])} | {np.median(t['python']) / np.median(t['device']):.2f} |")
-    lines += ["", "| arena | search_fused = 0, ms: median (min .. max) | search_fused = 1, ms: median (min .. max) | 0 / 1 |", "|---|---|---|---|"]
+    lines += ["", "| arena | search_fused = 0, ms: median (min .. max) | search_fused = 1, ms: median (min .. max) | search_fused = 2, ms: median (min .. max) | 0 / 1 | 1 / 2 |",
+              "|---|---|---|---|---|---|"]
     for what, t in fused_rows:
-        lines.append(f"| {what} | {ms(t['0'])} | {ms(t['1'])} | {np.median(t['0']) / np.median(t['1']):.2f} |")
+        lines.append(f"| {what} | {ms(t['0'])} | {ms(t['1'])} | {ms(t['2'])} | {np.median(t['0']) / np.median(t['1']):.2f} | {np.median(t['1']) / np.median(t['2']):.2f} |")
     text = "\n".join(lines)
     print(text)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         open(a.out, "w").write(text + "\n")
     print(json.dumps({what: {"python_ms": 1e3 * float(np.median(t["python"])), "device_ms": 1e3 * float(np.median(t["device"]))} for what, t in rows}
-                     | {what: {"per_iteration_ms": 1e3 * float(np.median(t["0"])), "fused_ms": 1e3 * float(np.median(t["1"]))} for what, t in fused_rows}))
+                     | {what: {"per_iteration_ms": 1e3 * float(np.median(t["0"])), "fused_ms": 1e3 * float(np.median(t["1"])), "one_launch_ms": 1e3 * float(np.median(t["2"]))}
+                        for what, t in fused_rows}))
     for e in engines:
         e.close()
 
